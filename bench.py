@@ -1,29 +1,38 @@
 #!/usr/bin/env python3
 """Headline benchmark of the CFUN hot path on MI355X (BASELINE.json: volumes/sec, forward+backward).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed warm-up steps, times exactly K steps, writes what the last timed step computed when
+--dump-outputs DIR is given (see dump_outputs), and prints the result line: `metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` (milliseconds per timed step) and the workload's description.  Everything else the benchmark
+measures or checks runs only under --full: the roofline figures and their back-to-back kernel timings, the oracle's CPU
+baseline with the loss / gradient parity at full size, and at N > 1 the communication pre-flight, the parity of the
+sharded step and the extra one-volume leg.
 
 N > 1: either under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE from
-the environment; WORLD_SIZE must equal N) or as plain python -- the script then re-executes itself under that launcher,
-so `--gpus 8` can never print a one-rank number.  N ranks need N GPUs (CFUN_BENCH_BACKEND=gloo: smoke test on fewer).
+the environment; WORLD_SIZE must equal N) or as plain python -- the script then starts that launcher as a child process and
+exits with its status, so `--gpus 8` can never print a one-rank number.  N ranks need N GPUs (CFUN_BENCH_BACKEND=gloo:
+smoke test on fewer).
 
 A "step" = one synthetic 256x256x128 8-class CT volume through FPN -> RPN -> proposals/NMS -> classifier head
 (12 RoIs) -> U-Net mask head (4 positive RoIs, 96^3 in, 192^3 out, stage 'finetune') -> 6 losses incl. the
 3-D Sobel edge loss -> backward (cfun_amd.step.training_step); inputs are resident in HBM before the timed
 region, no optimizer step, no host sync inside a step except the NMS count read the reference also has.
-N > 1: one process per GPU; first a communication pre-flight (cfun_amd.dist_selftest: halo send/recv, candidate all-gather,
-bucketed all-reduce, sharded convs vs the un-sharded ones -> `preflight`, `rccl_ranks_seen`), then every rank trains its own
-volume (whole volumes are independent units) and the replicated weights' gradients are all-reduced over RCCL during each
-step's backward -- weak scaling, `value`.  The same invocation then times ONE volume per step over all ranks (depth-sharded,
-strong scaling) and reports it as `sharded_one_volume` with its parity against the single-process step (`sharded_parity`);
---sharded makes that figure `value` instead.
+N > 1: one process per GPU; with --full first a communication pre-flight (cfun_amd.dist_selftest: halo send/recv, candidate
+all-gather, bucketed all-reduce, sharded convs vs the un-sharded ones -> `preflight`, `rccl_ranks_seen`), then every rank
+trains its own volume (whole volumes are independent units) and the replicated weights' gradients are all-reduced over RCCL
+during each step's backward -- weak scaling, `value`.  With --full the same invocation then times ONE volume per step over all
+ranks (depth-sharded, strong scaling) and reports it as `sharded_one_volume` with its parity against the single-process step
+(`sharded_parity`); --sharded makes that figure `value` instead.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel, timed live with HIP
+Prints ONE JSON line (rank 0) with the contract fields; --full adds `roofline` (dominant kernel, timed live with HIP
 events on the launch stream) and, at N = 1, `cpu_baseline` (the oracle on the host cores, bounded sample).
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -434,13 +443,61 @@ def cpu_baseline(cfg, net, sample, threads, iters=1, small_iters=3, grad_keys=GR
     phys, logical = physical_cores()
     return dict(value=1.0 / med, unit="volumes/s", cores=threads, kind="port", physical_cores=phys, logical_cpus=logical,
                 sample="oracle (torch %s CPU fp32, torch.get_num_threads() = %d threads on a host with %d physical cores / "
-                       "%d logical CPUs -- one thread per physical core, capped at 64: past that torch's CPU conv3d / "
-                       "instance-norm kernels stop scaling): the identical %dx%dx%d '%s' training step -- same "
-                       "weights, image, 4 + 8 RoIs, targets, Dropout3d masks (seed 1), six losses, forward + backward; %d "
+                       "%d logical CPUs -- one thread per physical core, capped at 64 (past that torch's CPU conv3d / "
+                       "instance-norm kernels stop scaling) and at OMP_NUM_THREADS when set): the identical %dx%dx%d '%s' "
+                       "training step -- same weights, image, 4 + 8 RoIs, targets, Dropout3d masks (seed 1), six losses, forward + backward; %d "
                        "timed full iteration(s) after a warm-up at 64x64x32: %s s (median %.1f s); nothing extrapolated"
                        % (torch.__version__, torch.get_num_threads(), phys, logical, h, w, d, cfg.STAGE, len(times),
                           ", ".join("%.1f" % t for t in times), med),
                 losses=losses, small_config=small, _grads=grads)
+
+
+DUMP_BUDGET_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+DUMP_MAX_ELEMS = 1 << 20         # elements kept of one array before the budget is shared out
+
+
+def dump_arrays(out, losses, total, net):
+    """[(name, tensor)] of what a caller of the timed path receives from one step: the six losses and their weighted total,
+    the tensors of the step's output dict (`out`; None for the sharded step, whose caller gets the losses and gradients) and
+    every parameter gradient."""
+    arrays = [("losses", torch.stack([l.detach().double().reshape(()) for l in losses]))]
+    if total is not None:
+        arrays.append(("total_loss", total.detach().double().reshape(1)))
+    for k in sorted(out or {}):
+        v = out[k]
+        if torch.is_tensor(v):
+            arrays.append(("out." + k, v.detach()))
+        elif isinstance(v, (list, tuple)):
+            arrays += [("out.%s.%d" % (k, i), t.detach()) for i, t in enumerate(v) if torch.is_tensor(t)]
+    arrays += [("grad." + k, p.grad.detach()) for k, p in net.named_parameters() if p.grad is not None]
+    return arrays
+
+
+def dump_outputs(dirname, arrays):
+    """Writes every (name, tensor) as DIR/<name>.npy: float64 stays float64, other floating types become float32, integer and
+    bool tensors float64.  The files hold at most DUMP_BUDGET_BYTES in all: an array of more elements than its share (the
+    same share for every large array, halved from DUMP_MAX_ELEMS until the total fits) is written as a fixed sample of its
+    row-major flattening -- the sorted flat indices numpy.random.default_rng(0).choice(numel, share, replace=False) picks --
+    so two runs with the same arguments write arrays of the same shapes from the same positions."""
+    import numpy as np
+
+    def itemsize(t):
+        return 4 if t.is_floating_point() and t.dtype != torch.float64 else 8
+
+    cap = DUMP_MAX_ELEMS
+    while cap > 1 and sum(min(t.numel(), cap) * itemsize(t) for _, t in arrays) > DUMP_BUDGET_BYTES:
+        cap //= 2
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays:
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), cap, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.cpu()
+        a = (a.float() if itemsize(t) == 4 else a.double()).numpy()
+        if t.numel() <= cap:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(dirname, name.replace(os.sep, "_") + ".npy"), a)
 
 
 def free_port():
@@ -473,7 +530,14 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: roofline and back-to-back kernel "
+                         "timings, the oracle's CPU baseline with loss / gradient parity at full size (N = 1), the "
+                         "communication pre-flight, sharded-step parity and the one-volume leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (losses, the step's output tensors, the "
+                         "parameter gradients) as DIR/<name>.npy, at most 64 MB in all (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity at full size")
     ap.add_argument("--cpu-baseline-iters", type=int, default=0,
                     help="timed full iterations of the oracle's CPU step (median reported).  0 (default): 3 -- the median of 3 "
                          "warm iterations SURVEY.md section 8(d) asks for -- when the first one takes < 60 s on this host, "
@@ -521,12 +585,12 @@ def main():
     args = parse_args()
     backend = os.environ.get("CFUN_BENCH_BACKEND", "nccl")     # "nccl" is RCCL on ROCm; gloo: smoke test on fewer GPUs
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # started as plain `python bench.py --gpus N`: become the N-rank job (one process per GPU) instead of printing an
-        # N = 1 number under the wrong label
+        # started as plain `python bench.py --gpus N`: run the N-rank job (one process per GPU) as a child and pass its exit
+        # status on, instead of printing an N = 1 number under the wrong label
         if not args.preflight_only or torch.cuda.is_available():
             check_gpu_count(args.gpus, backend)
         sys.stdout.flush()
-        os.execve(sys.executable, launch_command(sys.argv[1:], args.gpus), dict(os.environ))
+        sys.exit(subprocess.run(launch_command(sys.argv[1:], args.gpus), env=dict(os.environ)).returncode)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -552,10 +616,11 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(backend, rank=rank, world_size=world)
         from cfun_amd import dist as cdist, dist_selftest
-        # every communication pattern of the path once, against single-process results, BEFORE anything is timed
-        preflight = dist_selftest.preflight(dev)
-        if rank == 0 and not preflight["ok"]:
-            sys.stderr.write("communication pre-flight FAILED: %s\n" % json.dumps(preflight))
+        if args.full or args.preflight_only:
+            # every communication pattern of the path once, against single-process results, BEFORE anything is timed
+            preflight = dist_selftest.preflight(dev)
+            if rank == 0 and not preflight["ok"]:
+                sys.stderr.write("communication pre-flight FAILED: %s\n" % json.dumps(preflight))
     elif args.preflight_only:
         raise SystemExit("--preflight-only needs --gpus N > 1")
     if args.preflight_only:
@@ -574,7 +639,7 @@ def main():
     sharded = args.sharded and world > 1
     sample = step.synthetic_inputs(cfg, dev, seed=0 if sharded else rank)
     assert sample["p_rois"].shape[0] == 4 and sample["n_rois"].shape[0] == 8   # heads must not be skipped
-    timer = ops.LaunchTimer(dominant_kernel_match(cfg))
+    timer = ops.LaunchTimer(dominant_kernel_match(cfg)) if args.full else None      # --full: the roofline's in-step timing
     # N > 1: data-parallel replicas (one volume per GPU).  Gradients are averaged in 64 MB flat buckets whose RCCL
     # all-reduce is issued on a side stream as soon as backward has filled them (cfun_amd.dist.GradientReducer)
     reducer = None
@@ -583,6 +648,8 @@ def main():
         reducer = cdist.GradientReducer(net.parameters(), average=not sharded)      # sharded: additive shares -> sum
 
     step_no = [0]
+    keep = [False]      # set for the last timed step under --dump-outputs: its results are kept in `last`
+    last = {}
 
     def one_sharded_step():     # the ranks' loss shares / gradients add up to the single-GPU step (the reducer sums)
         step_no[0] += 1
@@ -590,6 +657,8 @@ def main():
         with cdist.depth_sharded():
             losses, total, _ = cdist.sharded_training_step(net, sample_s, dropout_seed=step_no[0])
         reducer.finish()
+        if keep[0]:
+            last.update(out=None, total=total)
         return losses
 
     def one_step():
@@ -602,6 +671,8 @@ def main():
         out, losses, total = step.training_step(net, sample)
         if reducer is not None:
             reducer.finish()
+        if keep[0]:
+            last.update(out=out, total=total)
         return losses
 
     def fence():
@@ -610,15 +681,18 @@ def main():
             dist.barrier(device_ids=[local]) if backend == "nccl" else dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(fn, steps, warmup):
-        """`warmup` untimed steps, then exactly `steps` steps between barrier + synchronize on both sides; MAX over ranks."""
+    def timed(fn, steps, warmup, keep_last=False):
+        """`warmup` untimed steps, then exactly `steps` steps between barrier + synchronize on both sides; MAX over ranks.
+        `keep_last`: the last timed step leaves its results in `last`."""
         losses = None
         for _ in range(warmup):
             losses = fn()
         fence()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
+            keep[0] = keep_last and i == steps - 1
             losses = fn()
+        keep[0] = False
         fence()
         elapsed = time.perf_counter() - t0
         if world > 1:
@@ -632,29 +706,29 @@ def main():
         losses = one_step()
     fence()
     ops.set_launch_timer(timer)
-    elapsed, losses = timed(one_step, args.steps, 0)
+    elapsed, losses = timed(one_step, args.steps, 0, keep_last=args.dump_outputs is not None)
     ops.set_launch_timer(None)
     sharded_parity = None
     if sharded:
         lt = torch.stack([l.detach().float() for l in losses])      # the ranks' shares: report their sum
         dist.all_reduce(lt)
         losses = list(lt)
+    if args.dump_outputs is not None:
+        # before anything below runs another step: the last timed step's losses (at --sharded: the sum of the ranks' shares),
+        # outputs and gradients (rank 0's; all-reduced at N > 1)
+        arrays = dump_arrays(last.get("out"), losses, None if sharded else last.get("total"), net)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
+        del arrays
+        last.clear()
+    if sharded and args.full:
         sharded_parity = sharded_parity_check(cdist, step, dist, net, cfg, sample, reducer, one_sharded_step, rank, world)
         fence()
-    want_sharded_leg = world > 1 and not sharded and not args.no_sharded_leg and d % (16 * world) == 0
+    want_sharded_leg = (args.full and world > 1 and not sharded and not args.no_sharded_leg and d % (16 * world) == 0)
     lv = [float(l.detach()) for l in losses]
     assert all(v == v and abs(v) != float("inf") for v in lv), "non-finite loss: %s" % lv
 
     if rank == 0:
-        b = cfg.UNET_MASK_BRANCH_CHANNEL
-        side = cfg.MASK_POOL_SIZE
-        n_roi_launch = len(range(0, 4, world)) if sharded else 4                     # RoIs of rank 0's mask-head launches
-        flops = 2.0 * (2 * b) * (2 * b) * 27 * side[0] * side[1] * side[2] * n_roi_launch   # per launch
-        durs = timer.durations_ms("mfma")
-        durs_h = timer.durations_ms("hbm")
-        kern, executed, kname = dominant_kernel_info(cfg, n_roi_launch)
-        t_k = sum(durs) / max(len(durs), 1) * 1e-3
-        achieved = flops / t_k / 1e12 if t_k > 0 else 0.0
         result = {
             "metric": "volumes/sec fwd+bwd, 256x256x128 8-class CT" if args.workload == "cfg2"
                       else "volumes/sec fwd+bwd (%s)" % args.workload,
@@ -666,8 +740,8 @@ def main():
             "data": "synthetic",
             "config": {"workload": "%s: %dx%dx%d CT, stage '%s', 4 positive + 8 negative RoIs, U-Net b=%d, "
                                    "%s crops -> %s masks, 6 losses%s, fwd+bwd"
-                                   % (args.workload, h, w, d, stage, b, "x".join(map(str, side)),
-                                      "x".join(map(str, cfg.MASK_SHAPE)),
+                                   % (args.workload, h, w, d, stage, cfg.UNET_MASK_BRANCH_CHANNEL,
+                                      "x".join(map(str, cfg.MASK_POOL_SIZE)), "x".join(map(str, cfg.MASK_SHAPE)),
                                       " incl. 3-D Sobel edge loss" if stage == "finetune" else ""),
                        "parallelism": ("ONE volume over %d GPUs: depth-sharded FPN/RPN with xGMI halo exchange overlapped "
                                        "with the interior planes, RPN all-gather, classifier RoIs round-robin, every "
@@ -676,6 +750,25 @@ def main():
                                       ("1 volume per GPU x %d, bucketed gradient all-reduce (RCCL) overlapped with backward"
                                        % world) if world > 1 else "single GPU"},
             "losses": lv, "when": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime()),
+        }
+        if world > 1:
+            result["backend"] = backend + ("" if backend == "nccl" else " (NOT RCCL: %d ranks on %d device(s), collectives on "
+                                           "the host -- a smoke test of the N-rank path, not a scaling measurement)"
+                                           % (world, torch.cuda.device_count()))
+    else:
+        result = None
+    parity_fail = None
+    if rank == 0 and args.full:
+        b = cfg.UNET_MASK_BRANCH_CHANNEL
+        side = cfg.MASK_POOL_SIZE
+        n_roi_launch = len(range(0, 4, world)) if sharded else 4                     # RoIs of rank 0's mask-head launches
+        flops = 2.0 * (2 * b) * (2 * b) * 27 * side[0] * side[1] * side[2] * n_roi_launch   # per launch
+        durs = timer.durations_ms("mfma")
+        durs_h = timer.durations_ms("hbm")
+        kern, executed, kname = dominant_kernel_info(cfg, n_roi_launch)
+        t_k = sum(durs) / max(len(durs), 1) * 1e-3
+        achieved = flops / t_k / 1e12 if t_k > 0 else 0.0
+        result.update({
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved / PEAK_FP32_MFMA_TFLOPS,
                          "traffic": None, "mfma_util_pmc": None,
@@ -690,7 +783,7 @@ def main():
                                       "of the matrix pipe it keeps busy is `mfma_pipe_frac` (instruction count) / "
                                       "`mfma_util_pmc` (SQ_VALU_MFMA_BUSY_CYCLES) -- read those as the utilisation figure",
                          "avg_launch_ms": t_k * 1e3, "launches_timed": len(durs)},
-        }
+        })
         if args.workload == "cfg2" and not args.no_hbm_loop and kern == 2:
             # the same conv back to back outside the step: kernel only (comparable to rocprofv3's per-kernel average under
             # profiles/) and with the per-call weight transform a caller outside a WeightScope pays
@@ -784,7 +877,10 @@ def main():
             gg = {k: named[k].grad.detach().cpu().clone() for k in pkeys if k in named and named[k].grad is not None}
             torch.cuda.empty_cache()
             phys, _ = physical_cores()
-            cb = cpu_baseline(cfg, net, sample, threads=max(1, min(phys, 64)), iters=args.cpu_baseline_iters, grad_keys=pkeys)
+            threads = min(phys, 64)
+            if os.environ.get("OMP_NUM_THREADS", "").isdigit():     # a host that grants this process fewer CPUs than it has
+                threads = min(threads, int(os.environ["OMP_NUM_THREADS"]))
+            cb = cpu_baseline(cfg, net, sample, threads=max(1, threads), iters=args.cpu_baseline_iters, grad_keys=pkeys)
             cg = cb.pop("_grads") or {}
             result["cpu_baseline"] = cb
             rel = [abs(g - c) / max(abs(c), 1e-12) for g, c in zip(gl, cb["losses"])]
@@ -836,8 +932,6 @@ def main():
                                            % (world, preflight["devices_seen"]))
             if not preflight["ok"] and parity_fail is None:
                 parity_fail = "communication pre-flight FAILED: %s" % preflight["max_rel_err"]
-    else:
-        result, parity_fail = None, None
 
     if want_sharded_leg:
         # the OTHER curve SURVEY.md section 8(e) asks to report, from the same invocation: ONE volume per step over all ranks

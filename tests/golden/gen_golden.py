@@ -866,10 +866,157 @@ def case_unmold_lits():
          boxes=boxes, class_ids=ids, scores=scores, class_map=cmap.astype(np.uint8))
 
 
+def dropin_cfg(stage="beginning"):
+    """The shrunken HeartConfig of the drop-in fixtures (tests/test_dropin_reference.py builds the same one from cfun_amd.config)."""
+    return make_cfg(stage, 32, 16, MASK_POOL_SIZE=[32, 32, 32], POOL_SIZE=[4, 4, 4], UNET_MASK_BRANCH_CHANNEL=4,
+                    TOP_DOWN_PYRAMID_SIZE=16, RPN_CONV_CHANNELS=16, FPN_CLASSIFY_FC_LAYERS_SIZE=16, RPN_ANCHOR_SCALES=(16, 32))
+
+
+def _sub(name, t, step=4):
+    """A large 5-D output as a strided subsample + fp64 checksums (sum, sum |.|)."""
+    a = t.detach().numpy()
+    return {name + "_sub": a[:, :, ::step, ::step, ::step].copy(),
+            name + "_sum": np.array([a.astype(np.float64).sum(), np.abs(a).astype(np.float64).sum()])}
+
+
+def case_dropin():
+    """INTEGRATION.md section 1's module-level swaps, recorded at their interfaces on the reference's own classes (closed-form
+    weights, the tiny configuration of dropin_cfg): what model.FPN hands the backbone stages and gets back, what model.Mask
+    hands RoI_Align and the U-Net and gets back, the arguments and result of proposal_layer's utils.non_max_suppression
+    call, and the whole MaskRCNN training step (predict('training') -> compute_losses -> backward) with its randperm draws
+    and Dropout3d masks.  tests/test_dropin_reference.py holds cfun_amd's drop-ins to these without the reference."""
+    cfg = dropin_cfg()
+    # (1) model.FPN on the P3D19 stages
+    fpn = ref_model.FPN(*ref_backbone.P3D19(config=cfg).stages(), out_channels=16, config=cfg)
+    shapes = load_formula(fpn)
+    fpn.eval()
+    x = torch.from_numpy(formula.uniform("dropin.fpn.x", (1, 1, 16, 32, 32), -2, 2))
+    with torch.no_grad():
+        c1 = fpn.C1(x)
+        c2 = fpn.C2(c1)
+        c3 = fpn.C3(c2)
+        p2, p3 = fpn(x)
+    save("dropin_fpn", x=x.numpy(), c1=c1.numpy(), c2=c2.numpy(), c3=c3.numpy(), p2=p2.numpy(), p3=p3.numpy(),
+         **shapes_to_npz(shapes))
+
+    # (2) model.Mask: RoI_Align of the raw image -> mask_branch.Modified3DUNet -> softmax
+    mask = ref_model.Mask(1, [32, 32, 32], 8, 4, "beginning")
+    shapes = load_formula(mask)
+    mask.eval()
+    img = torch.from_numpy(formula.uniform("dropin.mask.img", (1, 1, 16, 32, 32), -2, 2))
+    rois = torch.tensor([[0.0, 0.1, 0.1, 1.0, 0.9, 0.8], [0.2, 0.0, 0.3, 0.9, 0.6, 1.0]])   # [n,6] as in training
+    calls, unet_io = [], []
+    orig_align = ref_model.RoI_Align
+
+    def rec_align(feature_map, pool_size, boxes):
+        out = orig_align(feature_map, pool_size, boxes)
+        calls.append((feature_map.detach().clone(), np.array(pool_size), boxes.detach().clone(), out.detach().clone()))
+        return out
+    ref_model.RoI_Align = rec_align
+    hook = mask.modified_u_net.register_forward_hook(lambda m, i, o: unet_io.append((i[0].detach().clone(), o.detach().clone())))
+    try:
+        with torch.no_grad():
+            logits, probs = mask([img, img], rois)
+    finally:
+        ref_model.RoI_Align = orig_align
+        hook.remove()
+    assert len(calls) == 1 and len(unet_io) == 1
+    fm, pool, boxes, aligned = calls[0]
+    arrs = dict(img=img.numpy(), rois=rois.numpy(), align_fm=fm.numpy(), align_pool=pool, align_boxes=boxes.numpy(),
+                align_out=aligned.numpy(), unet_in=unet_io[0][0].numpy(), **shapes_to_npz(shapes))
+    arrs.update(_sub("unet_out", unet_io[0][1]))
+    arrs.update(_sub("logits", logits))
+    arrs.update(_sub("probs", probs))
+    save("dropin_mask", **arrs)
+
+    # (3) model.proposal_layer's utils.non_max_suppression call
+    bshapes = ref_model.compute_backbone_shapes(cfg, cfg.IMAGE_SHAPE)
+    anchors = ref_utils.generate_pyramid_anchors(cfg.RPN_ANCHOR_SCALES, cfg.RPN_ANCHOR_RATIOS, bshapes,
+                                                 cfg.BACKBONE_STRIDES, cfg.RPN_ANCHOR_STRIDE).astype(np.float32)
+    a = anchors.shape[0]
+    probs = torch.softmax(torch.from_numpy(formula.uniform("dropin.logits", (1, a, 2), -3, 3)), dim=2)
+    bbox = torch.from_numpy(formula.uniform("dropin.bbox", (1, a, 6), -1, 1))
+    nms_calls = []
+    orig_nms = ref_utils.non_max_suppression
+
+    def rec_nms(boxes, scores, threshold, max_num):
+        keep = orig_nms(boxes, scores, threshold, max_num)
+        nms_calls.append((np.array(boxes, np.float32), np.array(scores, np.float32), float(threshold), int(max_num),
+                          np.array(keep)))
+        return keep
+    ref_utils.non_max_suppression = rec_nms
+    try:
+        want = ref_model.proposal_layer([probs.clone(), bbox.clone()], proposal_count=12, nms_threshold=0.7,
+                                        anchors=torch.from_numpy(anchors), config=cfg)
+    finally:
+        ref_utils.non_max_suppression = orig_nms
+    assert len(nms_calls) == 1
+    nb, ns, thr, mx, keep = nms_calls[0]
+    save("dropin_proposal", anchors=anchors, probs=probs.numpy(), bbox=bbox.numpy(), nms_boxes=nb, nms_scores=ns,
+         nms_cfg=np.array([thr, mx], np.float64), nms_keep=keep, rois=want.numpy())
+
+    # (4) the whole MaskRCNN training step
+    cfg = dropin_cfg()
+    cfg.MASK_SHAPE = cfg.MINI_MASK_SHAPE = (32, 32, 32)
+    cfg.POST_NMS_ROIS_TRAINING = 64
+    net = ref_model.MaskRCNN(cfg, "/tmp/cfun_logs", test_flag=False)
+    shapes = load_formula(net)
+    with torch.no_grad():                       # keep the proposals near their anchors so that positives exist
+        net.rpn.conv_bbox.weight.mul_(0.05)
+    H, W, D = [int(v) for v in cfg.IMAGE_SHAPE[:3]]
+    lab = np.zeros((D, H, W), np.int64)
+    for k in range(1, 8):
+        lab[:, :, (k - 1) * W // 7:k * W // 7] = k
+    hu = np.where(lab == 0, -1000.0, (lab - 1) * 50.0) + formula.uniform("dropin.noise", (D, H, W), -50, 50)
+    img = ((hu - hu.mean()) / hu.std()).astype(np.float32)
+    gt_masks = np.stack([(lab == k) for k in range(8)], axis=0).astype(np.float32)[None]
+    gt_boxes = np.tile(np.array([0, 0, 0, D, H, W], np.float32), (7, 1))[None]
+    gt_ids = np.arange(1, 8, dtype=np.int32)[None]
+    torch.manual_seed(5)
+    with PermRecorder() as perms, DropRecorder() as drops:
+        outs = net.predict([torch.from_numpy(img)[None, None], None, torch.from_numpy(gt_ids), torch.from_numpy(gt_boxes),
+                            torch.from_numpy(gt_masks)], "training")
+    assert outs[8].numel() > 0, "the reference's heads were skipped (no positive RoI): the fixture would be void"
+    a = net.anchors.shape[0]
+    rpn_match = np.zeros((1, a, 1), np.int32)
+    rpn_match[0, ::5, 0] = 1
+    rpn_match[0, 1::5, 0] = -1
+    rpn_bbox = formula.uniform("dropin.rpnb", (1, cfg.RPN_TRAIN_ANCHORS_PER_IMAGE, 6), -1, 1)
+    losses = ref_model.compute_losses(torch.from_numpy(rpn_match), torch.from_numpy(rpn_bbox), *outs, "beginning")
+    keys = ("rpn_class_loss", "rpn_bbox_loss", "mrcnn_class_loss", "mrcnn_bbox_loss", "mrcnn_mask_loss", "mrcnn_mask_edge_loss")
+    total = sum(cfg.LOSS_WEIGHTS[k] * l for k, l in zip(keys, losses))
+    total.backward()
+    (rpn_class_logits, rpn_pred_bbox, target_class_ids, mrcnn_class_logits, target_deltas, mrcnn_bbox,
+     target_mask, mrcnn_mask, mrcnn_mask_logits) = outs
+    tm = target_mask.numpy()
+    arrs = dict(image=img, gt_masks_labels=lab.astype(np.uint8), gt_boxes=gt_boxes, gt_class_ids=gt_ids,
+                rpn_match=rpn_match, rpn_bbox_t=rpn_bbox,
+                rpn_class_logits=rpn_class_logits.detach().numpy(), rpn_pred_bbox=rpn_pred_bbox.detach().numpy(),
+                target_class_ids=target_class_ids.numpy(), mrcnn_class_logits=mrcnn_class_logits.detach().numpy(),
+                target_deltas=target_deltas.numpy(), mrcnn_bbox=mrcnn_bbox.detach().numpy(),
+                target_mask_labels=tm.argmax(1).astype(np.uint8), target_mask_is_onehot=np.array(bool(np.all(tm.sum(1) == 1))),
+                losses=np.array([float(l) for l in losses]), total=np.array(float(total)),
+                n_pos=np.array(int((target_class_ids > 0).sum())), n_rois=np.array(int(target_class_ids.shape[0])),
+                **shapes_to_npz(shapes))
+    arrs.update(_sub("mask_logits", mrcnn_mask_logits))
+    arrs.update(_sub("mask_probs", mrcnn_mask))
+    for i, p in enumerate(perms.perms):
+        arrs["randperm%d" % i] = p
+    for i, m in enumerate(drops.masks):
+        arrs["drop%d" % i] = m.numpy()
+    for k, p in net.named_parameters():
+        if p.grad is not None:
+            g = p.grad.numpy()
+            arrs[("grad4:" if g.size > 20000 else "grad:") + k] = g[::4, ::4].copy() if g.size > 20000 else g
+    print("dropin step: n_pos", int(arrs["n_pos"]), "n_rois", int(arrs["n_rois"]), "losses", arrs["losses"].tolist(),
+          "grads", sum(1 for k in arrs if k.startswith("grad")))
+    save("dropin_step", **arrs)
+
+
 CASES = dict(fpn_rpn_lits=case_fpn_rpn_lits, unet_lits=case_unet_lits, dtl_lits=case_dtl_lits, predict_lits=case_predict_lits,
              losses_lits=case_losses_lits, unmold_lits=case_unmold_lits, unmold=case_unmold, refine=case_refine, nms=case_nms, anchors=case_anchors, roi_align=case_roi_align, fpn_rpn=case_fpn_rpn, unet=case_unet,
              losses=case_losses, proposal=case_proposal, classifier=case_classifier, predict=case_predict,
-             train_epoch=case_train_epoch)
+             train_epoch=case_train_epoch, dropin=case_dropin)
 
 if __name__ == "__main__":
     torch.set_num_threads(8)

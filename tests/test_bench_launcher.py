@@ -2,7 +2,7 @@
 
 Until round 6 `--gpus` was parsed and never read -- the world size came from WORLD_SIZE alone, so a plain-python
 `bench.py --gpus 8` printed a one-rank number.  Held here, without a GPU:
-  * plain python with N > 1 re-executes itself under torch.distributed.run with N ranks (the real launch, end to end:
+  * plain python with N > 1 starts torch.distributed.run with N ranks as a child process (the real launch, end to end:
     `--preflight-only` on CPU tensors through the HIP emulator build, gloo) and the line says n_gpus = N with the
     communication pre-flight (cfun_amd.dist_selftest) green on every section;
   * WORLD_SIZE that disagrees with --gpus is refused, as are more ranks than GPUs over RCCL;
@@ -72,3 +72,42 @@ def test_no_gpu_no_number():
         pytest.skip("GPU present")
     r = _run(["--steps", "1"], {})
     assert r.returncode != 0 and b"needs a GPU" in r.stderr and not [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+
+
+def test_plain_run_options():
+    """A plain run is the headline figure only; --full and --dump-outputs are opt-in."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.steps == 3 and a.warmup == 1 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_float_arrays_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs writes one float32 / float64 .npy per array, within the byte budget, and the sample it keeps of a large
+    array is the same from run to run (two builds are compared output for output)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1 << 20)
+    gen = torch.Generator().manual_seed(0)
+    arrays = [("losses", torch.arange(6, dtype=torch.float64)), ("out.big", torch.randn(3, 200000, generator=gen)),
+              ("out.ids", torch.arange(10, dtype=torch.int32)), ("grad.w", torch.randn(4, 5, generator=gen))]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n, _ in arrays)
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64), f
+        np.testing.assert_array_equal(a, b)
+        total += a.nbytes
+    assert total <= 1 << 20
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "grad.w.npy"), arrays[3][1].numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "losses.npy"), np.arange(6.0))
+    assert np.load(tmp_path / "a" / "out.ids.npy").dtype == np.float64
+    big = np.load(tmp_path / "a" / "out.big.npy")
+    assert big.ndim == 1 and 0 < big.size < 600000 and np.isin(big, arrays[1][1].numpy().reshape(-1)).all()

@@ -91,7 +91,8 @@ def test_four_ranks_on_real_kernels(gpu, tmp_path):
 
 
 def _bench(args, env_extra, timeout):
-    """`python bench.py ...` as PLAIN python (no torchrun): the script launches its ranks itself.  Returns the JSON line."""
+    """`python bench.py ...` as PLAIN python (no torchrun): the script launches its ranks itself.  Returns the JSON line.
+    (The pre-flight, the sharded parity and the one-volume leg these tests read are --full's.)"""
     import json
     import subprocess
     import sys
@@ -108,7 +109,7 @@ def test_bench_plain_python_gpus2_is_a_two_rank_job(gpu):
     """`python bench.py --gpus 2` (no torchrun) on the real kernels -- two ranks on this box's one GPU,
     collectives over gloo -- prints n_gpus = 2, has run the communication pre-flight, and the same invocation carries BOTH
     curves: the data-parallel `value` and the one-volume `sharded_one_volume` with its parity against the single-process step."""
-    d = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg1"], dict(CFUN_BENCH_BACKEND="gloo"), 1500)
+    d = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg1"], dict(CFUN_BENCH_BACKEND="gloo"), 1500)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert d["preflight"]["ok"] and d["preflight"]["ranks_seen"] == 2 and d["rccl_ranks_seen"] == 0 and "NOT RCCL" in d["backend"]
     leg = d["sharded_one_volume"]
@@ -121,7 +122,7 @@ def test_bench_cfg3_one_volume_over_eight_ranks(gpu):
     """BASELINE configs[3] in its specified form inside the driver-run tier: ONE 512x512x256 volume
     depth-sharded over 8 ranks (32 input planes = 2 p3 planes per rank, 4 RoIs x 2 ranks z-sharded U-Nets), 2 timed steps;
     the summed loss shares reproduce the single-process step.  (8 processes on this box's one GPU, gloo.)"""
-    d = _bench(["--gpus", "8", "--sharded", "--workload", "cfg3", "--steps", "2", "--warmup", "1"],
+    d = _bench(["--full", "--gpus", "8", "--sharded", "--workload", "cfg3", "--steps", "2", "--warmup", "1"],
                dict(CFUN_BENCH_BACKEND="gloo"), 2400)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["steps"] == 2
     assert d["preflight"]["ok"] and d["preflight"]["ranks_seen"] == 8
@@ -133,7 +134,7 @@ def test_bench_cfg4_one_volume_over_eight_ranks(gpu):
     """BASELINE configs[4] ("LiTS_2017 config, same pipeline, 8x MI355X") the same way: the fork's 320x320x256 volume, P3D35 with
     the 5x7x7 stem, 3 classes, 32x80x80 crops, class-weighted CE, as ONE volume over 8 ranks (gloo on this box's one GPU); the
     summed loss shares reproduce the single-process step."""
-    d = _bench(["--gpus", "8", "--sharded", "--workload", "cfg4", "--steps", "2", "--warmup", "1"],
+    d = _bench(["--full", "--gpus", "8", "--sharded", "--workload", "cfg4", "--steps", "2", "--warmup", "1"],
                dict(CFUN_BENCH_BACKEND="gloo"), 2400)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["preflight"]["ok"]
     assert d["sharded_parity"]["ok"], d["sharded_parity"]

@@ -1,8 +1,9 @@
 #!/bin/bash
 # bench.py's data-parallel line WITH its one-volume leg on 4 and 8 gloo ranks sharing one GPU (plain python: the script launches itself)
-mkdir -p gpurun_out/r6m
+export OUT=${OUT:-bench_logs}      # where the logs of this script go
+mkdir -p $OUT/r6m
 for n in 4 8; do
-  ( CFUN_BENCH_BACKEND=gloo timeout 1200 python bench.py --gpus $n --steps 2 --warmup 1 2>&1 | grep -v amdgpu.ids | tail -1 ) > gpurun_out/r6m/bench_gpus${n}_gloo.json 2>&1
+  ( CFUN_BENCH_BACKEND=gloo timeout 1200 python bench.py --full --gpus $n --steps 2 --warmup 1 2>&1 | grep -v amdgpu.ids | tail -1 ) > $OUT/r6m/bench_gpus${n}_gloo.json 2>&1
   python - gpurun_out/r6m/bench_gpus${n}_gloo.json <<'PY'
 import json, sys
 try:
