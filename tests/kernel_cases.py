@@ -489,8 +489,9 @@ def check_mask_losses(device, logits_ncdhw, labels, expect=None):
     (0.7 * ce2 + 1.3 * el2).backward()
     assert_close(ld.grad, 0.7 * g_ce + 1.3 * g_el, "fused d(CE+Edge)/dlogits", 1e-5)
     assert_close(ld.grad.permute(0, 4, 1, 2, 3), 0.7 * g_ce_r + 1.3 * g_el_r, "fused vs oracle", 1e-3)
-    # round 6: ONE forward pass (softmax + CE + edge loss) and ONE backward pass that recomputes the edge coefficients
-    # (cfun_mask_fused_fwd / _bwd) against the separate kernels: identical probabilities, same losses, same gradient
+    # round 6: ONE forward pass (softmax + CE + edge loss) and ONE backward pass over the field the training forward leaves
+    # behind (cfun_mask_fused_fwd / _bwd; nothing is recomputed) against the separate kernels: same probabilities to a few ulp,
+    # same losses, same gradient
     if ops.mask_losses_fused_supported(ld):
         sep_grad = ld.grad.clone()
         ld.grad = None
