@@ -9,6 +9,7 @@ This module holds the convolution / normalisation / buffer / RoI / resize bindin
 ``WeightScope``) live in ``weights.py``, the mask-head losses in ``loss_ops.py``, the non-blocking host plumbing in
 ``hostio.py`` -- all re-exported here, so callers keep writing ``ops.<name>``.
 """
+import contextlib
 import ctypes as C
 import os
 from dataclasses import dataclass
@@ -79,7 +80,7 @@ def _params(spec, x_shape, has_scale, has_shift, has_res):
 
 
 def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
+    return t if t is None or t.is_contiguous() else t.contiguous()
 
 
 class LaunchTimer:
@@ -151,6 +152,22 @@ def set_launch_timer(timer):
     _TIMER = timer
 
 
+@contextlib.contextmanager
+def _record_launch(key):
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    yield
+    ev1.record()
+    _TIMER.add(key, ev0, ev1)
+
+
+def _timed(p, x, suffix=""):
+    """Context of one conv launch: its HIP events go to the launch timer under ``match(p) + suffix``; nothing when no
+    timer is set, x is not on the GPU or the timer does not match p."""
+    key = _TIMER.match(p) if (_TIMER is not None and x.is_cuda) else None
+    return _record_launch(key + suffix) if key else contextlib.nullcontext()
+
+
 class StatsSlot:
     """Receives InstanceNorm statistics (mean, rstd) [N,C,2] of a conv's OUTPUT from the epilogue that writes it
     (cfun_conv3d_fwd_fused, CfunConvFusion.out_stats) -- ``conv3d_w(..., stats=slot)`` fills it, ``instnorm_lrelu(y,
@@ -168,6 +185,17 @@ class StatsSlot:
             raise RuntimeError("StatsSlot: %d channels, the slot holds %d" % (c, self.stats.shape[1]))
         return self.stats[i:i + 1]
 
+    def claim(self, i, n, c, like):
+        """Where a conv over n samples with c output channels writes: the whole batch (i None) or row i, counted as filled."""
+        if (i is None and self.n != n) or (i is not None and n != 1):
+            raise RuntimeError("conv3d: stats slot of %d samples does not fit a conv over %d" % (self.n, n))
+        if i is None:
+            self.stats, self.filled = torch.empty((n, c, 2), dtype=torch.float32, device=like.device), self.n
+            return self.stats
+        dst = self.row(i, c, like)
+        self.filled += 1
+        return dst
+
     def get(self, n, c):
         """The finished [n,c,2] tensor, or None if not every row was filled by a fused epilogue."""
         if self.stats is None or self.filled != self.n or tuple(self.stats.shape) != (n, c, 2):
@@ -175,88 +203,112 @@ class StatsSlot:
         return self.stats
 
 
+@dataclass
+class _ConvCall:
+    """What conv3d / conv3d_w settle once per call and hand to _Conv3d beside its tensors."""
+    spec: ConvSpec
+    p: ConvParams
+    out: object = None          # a dense tensor to write y into, or (BatchBuffer, i)
+    dx_slot: tuple = None       # (BatchBuffer, i) that receives the input gradient
+    stats: object = None        # StatsSlot or (slot, i); set only when the conv's kernel has the statistics epilogue
+    pro: tuple = None           # (stats [N,Ci,2] or None, act, slope): the conv reads act((x - mean) * rstd) in place of x
+    shift_scaled: bool = False
+
+
+_CONV_INPUTS = ("x", "wp", "scale", "shift", "res", "w_src", "call")      # the arguments of _Conv3d.forward, in order
+
+
+def _weight_operands(wp, w_src, p, need_x):
+    """(wp, wpT) of a conv.  An OIDHW weight ``w_src`` is packed here and its gradient comes back in OIDHW (one fused
+    pass); wpT, the data gradient's layout, comes out of the same launch when x needs a gradient."""
+    if w_src is None:
+        return wp, None
+    scope = WeightScope.current()
+    got = scope.lookup(w_src, p, need_x) if scope is not None else None
+    if got is not None:          # operands from the pass's batched preparation (the Winograd U etc., not plain packs)
+        wp, wpT, p.w_prepared = got
+        return wp, wpT
+    materialize_weight(w_src)
+    return _pack(w_src, both=True) if need_x else (_pack(w_src), None)
+
+
+def _conv_output(out, spec, p, x):
+    shape = (p.N, p.Do, p.Ho, p.Wo, p.Co)
+    if spec.d2s:
+        cq = spec.d2s_cq or p.Co // 8
+        return torch.empty((p.N, 2 * p.Do, 2 * p.Ho, 2 * p.Wo, cq), dtype=torch.float32, device=x.device)
+    if torch.is_tensor(out):     # write into a caller-provided dense region (a depth range of a larger buffer)
+        y = out.view(out.shape)
+        if tuple(y.shape) != shape or not y.is_contiguous():
+            raise RuntimeError("conv3d: out %s / contiguous=%s does not fit the result %s"
+                               % (tuple(y.shape), y.is_contiguous(), shape))
+        return y
+    if out is not None:          # write into sample `i` of a BatchBuffer (zero-copy batch join)
+        return out[0].sample(out[1], shape, x)
+    return torch.empty(shape, dtype=torch.float32, device=x.device)
+
+
+def _grad_prep(lib, dy, y, scale, act, rows, c, per, scale_mode, st, one_pass=False, d2s=False):
+    """dy -> (gp, g): gp = dy * act'(y) = dL/d(pre-activation), g = gp * scale = dL/d(conv sum), over [rows, c] with ``per``
+    rows per sample.  ``one_pass``: g straight from dy in ONE launch, returned for gp as well (the caller never needs gp by
+    itself).  ``d2s``: dy, y and gp are in y's hi-res layout -- the conv kernels take that and gather the parities."""
+    if one_pass:
+        g = torch.empty_like(dy)
+        check(lib.cfun_act_bwd(ptr(y), ptr(dy), ptr(scale), ptr(g), rows, c, per, act, LRELU_SLOPE, scale_mode, st),
+              "act_bwd(act, scale)")
+        return g, g
+    gp = dy
+    if act != ACT_NONE:
+        gp = torch.empty_like(dy)
+        check(lib.cfun_act_bwd(ptr(y), ptr(dy), None, ptr(gp), dy.numel() // dy.shape[-1], dy.shape[-1],
+                               per * (8 if d2s else 1), act, LRELU_SLOPE, 0, st), "act_bwd")
+    g = gp
+    if scale is not None:
+        g = torch.empty_like(dy)
+        check(lib.cfun_act_bwd(None, ptr(gp), ptr(scale), ptr(g), rows, c, per, ACT_NONE, LRELU_SLOPE, scale_mode, st),
+              "act_bwd(scale)")
+    return gp, g
+
+
+def _wgrad(lib, x, g, dst, oidhw, p, fz, st):
+    """The weight gradient of conv p into ``dst``, OIDHW or packed, on stream ``st``; ``fz``: the forward's input prologue on x."""
+    ws = workspace(lib.cfun_conv3d_bwd_weight_workspace_bytes(C.byref(p)), x)
+    check(lib.cfun_conv3d_bwd_weight_fused(ptr(x), ptr(g), ptr(dst), int(oidhw), C.byref(p),
+                                           None if fz is None else C.byref(fz), ptr(ws), ws.numel(), st), "conv3d_bwd_weight")
+
+
 class _Conv3d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, wp, scale, shift, res, spec, out=None, dx_slot=None, w_src=None, stats=None, pro=None,
-                shift_scaled=False):
-        # pro = (stats [N,Ci,2] or None, act, slope): the conv reads act((x - mean) * rstd) in place of x (NormedInput)
+    def forward(ctx, x, wp, scale, shift, res, w_src, call):
         lib = _lib.load()
-        x = _c(x)
-        wpT = None
-        scale = None if scale is None else _c(scale)
-        shift = None if shift is None else _c(shift)
-        res = None if res is None else _c(res)
-        p = _params(spec, x.shape, scale is not None, shift is not None, res is not None)
-        if w_src is not None:      # OIDHW weight: packed here, its gradient comes back in OIDHW (one fused pass)
-            scope = WeightScope.current()
-            got = scope.lookup(w_src, p, ctx.needs_input_grad[0]) if scope is not None else None
-            if got is not None:          # operands from the pass's batched preparation (the Winograd U etc., not plain packs)
-                wp, wpT, p.w_prepared = got
-            else:
-                materialize_weight(w_src)
-                if ctx.needs_input_grad[0]:      # the data gradient's layout in the same launch, kept for backward
-                    wp, wpT = _pack(w_src, both=True)
-                else:
-                    wp = _pack(w_src)
+        spec, p, pro = call.spec, call.p, call.pro
+        x, scale, shift, res = _c(x), _c(scale), _c(shift), _c(res)
+        wp, wpT = _weight_operands(wp, w_src, p, ctx.needs_input_grad[_CONV_INPUTS.index("x")])
         wp = _c(wp)
         if not (p.w_prepared & 1) and wp.shape != (p.kd * p.kh * p.kw, p.Ci, p.CoP):
             raise RuntimeError("packed weight %s does not match conv %s" % (tuple(wp.shape), spec))
-        if spec.d2s:
-            cq = spec.d2s_cq or p.Co // 8
-            y = torch.empty((p.N, 2 * p.Do, 2 * p.Ho, 2 * p.Wo, cq), dtype=torch.float32, device=x.device)
-        elif torch.is_tensor(out):   # write into a caller-provided dense region (a depth range of a larger buffer)
-            y = out.view(out.shape)
-            if tuple(y.shape) != (p.N, p.Do, p.Ho, p.Wo, p.Co) or not y.is_contiguous():
-                raise RuntimeError("conv3d: out %s / contiguous=%s does not fit the result %s"
-                                   % (tuple(y.shape), y.is_contiguous(), (p.N, p.Do, p.Ho, p.Wo, p.Co)))
-        elif out is not None:        # write into sample `i` of a BatchBuffer (zero-copy batch join)
-            y = out[0].sample(out[1], (p.N, p.Do, p.Ho, p.Wo, p.Co), x)
-        else:
-            y = torch.empty((p.N, p.Do, p.Ho, p.Wo, p.Co), dtype=torch.float32, device=x.device)
-        timed = _TIMER.match(p) if (_TIMER is not None and x.is_cuda) else None
-        if timed:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        if pro is not None or (stats is not None and (lib.cfun_conv3d_fused_support(C.byref(p)) & _lib.FUSE_OUT_STATS)):
-            # InstanceNorm statistics of y from this epilogue (the norm that follows skips its pass over y) and / or the
-            # norm + activation in front of this conv applied while x is staged
-            dst = None
-            if stats is not None and (lib.cfun_conv3d_fused_support(C.byref(p)) & _lib.FUSE_OUT_STATS):
-                slot, i = stats if isinstance(stats, tuple) else (stats, None)
-                if (i is None and slot.n != p.N) or (i is not None and p.N != 1):
-                    raise RuntimeError("conv3d: stats slot of %d samples does not fit a conv over %d" % (slot.n, p.N))
-                if i is None:
-                    slot.stats = torch.empty((p.N, y.shape[-1], 2), dtype=torch.float32, device=x.device)
-                    dst, slot.filled = slot.stats, slot.n
-                else:
-                    dst = slot.row(i, y.shape[-1], x)
-                    slot.filled += 1
-            fz = _lib.ConvFusion(None, 0, 0.0, None if dst is None else dst.data_ptr(), float(slot.eps) if dst is not None else 0.0)
-            if pro is not None:
-                pst = None if pro[0] is None else _c(pro[0])
-                if pst is not None and tuple(pst.shape) != (p.N, p.Ci, 2):
-                    raise RuntimeError("conv3d: input statistics %s do not fit x %s" % (tuple(pst.shape), tuple(x.shape)))
-                fz.in_stats, fz.in_act, fz.in_slope = (None if pst is None else pst.data_ptr()), int(pro[1]), float(pro[2])
-            ws = workspace(lib.cfun_conv3d_fwd_fused_workspace_bytes(C.byref(p), C.byref(fz)), x)
-            check(lib.cfun_conv3d_fwd_fused(ptr(x), ptr(wp), ptr(scale), ptr(shift), ptr(res), ptr(y), C.byref(p),
-                                            C.byref(fz), ptr(ws), ws.numel(), stream(x)), "conv3d_fwd_fused")
-        else:
-            ws = workspace(lib.cfun_conv3d_fwd_workspace_bytes(C.byref(p)), x)
-            check(lib.cfun_conv3d_fwd(ptr(x), ptr(wp), ptr(scale), ptr(shift), ptr(res), ptr(y), C.byref(p), ptr(ws),
-                                      ws.numel(), stream(x)), "conv3d_fwd")
-        if timed:
-            ev1.record()
-            _TIMER.add(timed, ev0, ev1)
-        ctx.spec = spec
-        ctx.p = p
+        y = _conv_output(call.out, spec, p, x)
+        # InstanceNorm statistics of y from this epilogue (the norm that follows skips its pass over y) and / or the
+        # norm + activation in front of this conv applied while x is staged; a plain conv passes no fusion at all
+        dst, eps = None, 0.0
+        if call.stats is not None:
+            slot, i = call.stats if isinstance(call.stats, tuple) else (call.stats, None)
+            dst, eps = slot.claim(i, p.N, y.shape[-1], x), float(slot.eps)
+        pst, in_act, in_slope = (None, 0, 0.0) if pro is None else (_c(pro[0]), int(pro[1]), float(pro[2]))
+        fz = None
+        if pro is not None or dst is not None:
+            fz = C.byref(_lib.ConvFusion(None if pst is None else pst.data_ptr(), in_act, in_slope,
+                                         None if dst is None else dst.data_ptr(), eps))
+        with _timed(p, x):
+            ws = workspace(lib.cfun_conv3d_fwd_fused_workspace_bytes(C.byref(p), fz), x)
+            check(lib.cfun_conv3d_fwd_fused(ptr(x), ptr(wp), ptr(scale), ptr(shift), ptr(res), ptr(y), C.byref(p), fz,
+                                            ptr(ws), ws.numel(), stream(x)), "conv3d_fwd")
+        ctx.spec, ctx.p, ctx.dx_slot, ctx.shift_scaled = spec, p, call.dx_slot, bool(call.shift_scaled)
         ctx.res_shape = None if res is None else res.shape
-        ctx.dx_slot = dx_slot
         ctx.wshape = None if w_src is None else tuple(w_src.shape)
-        ctx.pro = None if pro is None else (int(pro[1]), float(pro[2]))
-        ctx.shift_scaled = bool(shift_scaled)
+        ctx.pro = None if pro is None else (in_act, in_slope)
         ctx.w_on_stream = bool(w_src is not None and getattr(w_src, "_cfun_wstream", False))
-        ctx.save_for_backward(x, wp if not (p.w_prepared & 1) else None, scale, y if spec.act != ACT_NONE else None, wpT,
-                              None if pro is None or pro[0] is None else _c(pro[0]))
+        ctx.save_for_backward(x, wp if not (p.w_prepared & 1) else None, scale, y if spec.act != ACT_NONE else None, wpT, pst)
         return y
 
     @staticmethod
@@ -264,114 +316,63 @@ class _Conv3d(torch.autograd.Function):
         lib = _lib.load()
         x, wp, scale, y, wpT, pst = ctx.saved_tensors
         spec, p = ctx.spec, ctx.p
-        fz = None
-        if ctx.pro is not None:      # the weight gradient stages x through the same prologue as the forward did
-            fz = _lib.ConvFusion(None if pst is None else pst.data_ptr(), ctx.pro[0], ctx.pro[1], None, 0.0)
-        need_x, need_w, need_scale, need_shift, need_res = ctx.needs_input_grad[:5]
-        need_wsrc = ctx.needs_input_grad[8]
-        if need_scale:
+        need = dict(zip(_CONV_INPUTS, ctx.needs_input_grad))
+        grad = dict.fromkeys(_CONV_INPUTS)
+        if need["scale"]:
             raise RuntimeError("cfun_amd conv3d: gradient w.r.t. the epilogue scale is not implemented "
                                "(BatchNorm is frozen on this path, model.py:1297-1304)")
-        dy = _c(dy)
+        # the weight gradient stages x through the same prologue as the forward did
+        fz = None if ctx.pro is None else _lib.ConvFusion(None if pst is None else pst.data_ptr(), *ctx.pro, None, 0.0)
+        dy, dhw = _c(dy), p.Do * p.Ho * p.Wo
         st = stream(dy)
-        nvox = p.N * p.Do * p.Ho * p.Wo
-        # gp = dL/d(pre-activation); g = gp * scale = dL/d(conv sum)
         # shift_scaled (the shift is t + b * scale of a folded BatchNorm, ops.fold_bias(..., pre=True)): db = scale * sum(gp)
         # = sum(g), so the pre-activation gradient is never needed by itself (unless a residual wants it) and g comes
         # out of ONE pass: g = dy * act'(y) * scale
-        one_pass = ctx.shift_scaled and scale is not None and not spec.d2s and not need_res
-        gp = dy
-        if one_pass:
-            g = torch.empty_like(dy)
-            check(lib.cfun_act_bwd(ptr(y) if spec.act != ACT_NONE else None, ptr(dy), ptr(scale), ptr(g), nvox, p.Co,
-                                   p.Do * p.Ho * p.Wo, spec.act, LRELU_SLOPE, p.scale_mode, st), "act_bwd(act, scale)")
-            gp = gp_out = g
-        else:
-            if spec.act != ACT_NONE:
-                gp = torch.empty_like(dy)
-                check(lib.cfun_act_bwd(ptr(y), ptr(dy), None, ptr(gp), dy.numel() // dy.shape[-1], dy.shape[-1],
-                                       p.Do * p.Ho * p.Wo * (8 if spec.d2s else 1), spec.act, LRELU_SLOPE, 0, st), "act_bwd")
-            gp_out = gp     # for d2s convs the kernels take the gradient in y's hi-res layout and gather the parities
-            g = gp
-            if scale is not None:
-                g = torch.empty_like(dy)
-                check(lib.cfun_act_bwd(None, ptr(gp), ptr(scale), ptr(g), nvox, p.Co, p.Do * p.Ho * p.Wo, ACT_NONE,
-                                       LRELU_SLOPE, p.scale_mode, st), "act_bwd(scale)")
-        def run_wgrad(st):
+        one_pass = ctx.shift_scaled and scale is not None and not spec.d2s and not need["res"]
+        gp, g = _grad_prep(lib, dy, y, scale, spec.act, p.N * dhw, p.Co, dhw, p.scale_mode, st, one_pass, spec.d2s)
+
+        def oidhw_grad(st):
             dw = torch.empty(ctx.wshape, dtype=torch.float32, device=dy.device)
-            if fz is not None:
-                ws = workspace(lib.cfun_conv3d_bwd_weight_workspace_bytes(C.byref(p)), x)
-                check(lib.cfun_conv3d_bwd_weight_fused(ptr(x), ptr(g), ptr(dw), 1, C.byref(p), C.byref(fz), ptr(ws),
-                                                       ws.numel(), st), "conv3d_bwd_weight_fused(oidhw)")
-            else:
-                nb = lib.cfun_conv3d_bwd_weight_workspace_bytes(C.byref(p))
-                ws = workspace(nb, x)
-                tk = _TIMER.match(p) if (_TIMER is not None and x.is_cuda) else None
-                if tk:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                check(lib.cfun_conv3d_bwd_weight_oidhw(ptr(x), ptr(g), ptr(dw), C.byref(p), ptr(ws), ws.numel(), st),
-                      "conv3d_bwd_weight_oidhw")
-                if tk:
-                    e1.record()
-                    _TIMER.add(tk + "_wgrad", e0, e1)
+            with _timed(p, x, "_wgrad"):
+                _wgrad(lib, x, g, dw, True, p, fz, st)
             return dw
-        dx = dwp = dshift = dres = dw = None
         # the weight gradient on its own stream, enqueued BEFORE the data gradient (see WGRAD_STREAM / _OnWgradStream)
         side_w = None
-        if need_wsrc and ctx.w_on_stream:
+        if need["w_src"] and ctx.w_on_stream:
             cur_s = torch.cuda.current_stream(dy.device)
             side_w = wgrad_stream(dy.device, cur_s)
             side_w.wait_stream(cur_s)            # g (and x) are complete
             with torch.cuda.stream(side_w):
-                dw = run_wgrad(side_w.cuda_stream)
+                grad["w_src"] = oidhw_grad(side_w.cuda_stream)
             for t in (x, g, pst):
                 if t is not None:
                     t.record_stream(side_w)
-        if need_x:
+        if need["x"]:
             # dx of a per-sample conv goes straight into its sample of the batch's gradient (zero-copy batch split)
             dx = torch.empty_like(x) if ctx.dx_slot is None else ctx.dx_slot[0].sample(ctx.dx_slot[1], x.shape, x)
             if wpT is None:
                 if wp is None:
                     raise RuntimeError("conv3d backward: no weight operand was kept for the data gradient")
                 wpT = _transpose_pack(wp, p.Co)
-            nb = lib.cfun_conv3d_bwd_data_workspace_bytes(C.byref(p))
-            ws = workspace(nb, x)
-            tk = _TIMER.match(p) if (_TIMER is not None and x.is_cuda) else None
-            if tk:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            check(lib.cfun_conv3d_bwd_data(ptr(g), ptr(wpT), ptr(dx), C.byref(p), ptr(ws), ws.numel(), st),
-                  "conv3d_bwd_data")
-            if tk:
-                e1.record()
-                _TIMER.add(tk + "_dgrad", e0, e1)
-        if need_w:
-            dwp = torch.empty_like(wp)
-            nb = lib.cfun_conv3d_bwd_weight_workspace_bytes(C.byref(p))
-            ws = workspace(nb, x)
-            if fz is not None:
-                check(lib.cfun_conv3d_bwd_weight_fused(ptr(x), ptr(g), ptr(dwp), 0, C.byref(p), C.byref(fz), ptr(ws),
-                                                       ws.numel(), st), "conv3d_bwd_weight_fused")
-            else:
-                check(lib.cfun_conv3d_bwd_weight(ptr(x), ptr(g), ptr(dwp), C.byref(p), ptr(ws), ws.numel(), st),
-                      "conv3d_bwd_weight")
-        if need_wsrc and side_w is None:
-            dw = run_wgrad(st)
-        if need_shift:      # (shift_scaled: db = sum(g) whichever way g was formed)
-            dshift = channel_sum((g if ctx.shift_scaled and scale is not None else gp).view(-1, p.Co))
-        if need_res:
-            if spec.d2s:
-                dres = torch.empty(ctx.res_shape, dtype=torch.float32, device=dy.device)
-                check(lib.cfun_upsample2_bwd(ptr(gp_out), ptr(dres), p.N, p.Do, p.Ho, p.Wo, gp_out.shape[-1], st),
-                      "upsample2_bwd")
-            elif p.res_up2:
-                dres = torch.empty(ctx.res_shape, dtype=torch.float32, device=dy.device)
-                check(lib.cfun_upsample2_bwd(ptr(gp), ptr(dres), p.N, p.Do // 2, p.Ho // 2, p.Wo // 2, p.Co, st),
-                      "upsample2_bwd")
-            else:
-                dres = gp
-        return dx, dwp, None, dshift, dres, None, None, None, dw, None, None, None
+            ws = workspace(lib.cfun_conv3d_bwd_data_workspace_bytes(C.byref(p)), x)
+            with _timed(p, x, "_dgrad"):
+                check(lib.cfun_conv3d_bwd_data(ptr(g), ptr(wpT), ptr(dx), C.byref(p), ptr(ws), ws.numel(), st),
+                      "conv3d_bwd_data")
+            grad["x"] = dx
+        if need["wp"]:
+            grad["wp"] = torch.empty_like(wp)
+            _wgrad(lib, x, g, grad["wp"], False, p, fz, st)
+        if need["w_src"] and side_w is None:
+            grad["w_src"] = oidhw_grad(st)
+        if need["shift"]:      # (shift_scaled: db = sum(g) whichever way g was formed)
+            grad["shift"] = channel_sum((g if ctx.shift_scaled and scale is not None else gp).view(-1, p.Co))
+        if need["res"] and (spec.d2s or p.res_up2):      # (d2s: gp is in y's hi-res layout)
+            do, ho, wo, c = (p.Do, p.Ho, p.Wo, gp.shape[-1]) if spec.d2s else (p.Do // 2, p.Ho // 2, p.Wo // 2, p.Co)
+            grad["res"] = torch.empty(ctx.res_shape, dtype=torch.float32, device=dy.device)
+            check(lib.cfun_upsample2_bwd(ptr(gp), ptr(grad["res"]), p.N, do, ho, wo, c, st), "upsample2_bwd")
+        elif need["res"]:
+            grad["res"] = gp
+        return tuple(grad.values())
 
 
 class NormedInput:
@@ -433,16 +434,36 @@ class _Materialize(torch.autograd.Function):
         return dy, None, None, None
 
 
-def _fusable_input(x, spec, scale, shift, res, need_wgrad):
-    """Can the conv (spec) stage the NormedInput x through its prologue -- forward kernel and, when the weight needs a
-    gradient, the weight-gradient kernel?"""
-    if spec.up2:
-        return False
-    lib = _lib.load()
-    p = _params(spec, x.shape, scale is not None, shift is not None, res is not None)
-    have = lib.cfun_conv3d_fused_support(C.byref(p))
+def _takes_prologue(spec, have, need_wgrad):
+    """Do the support bits ``have`` (cfun_conv3d_fused_support) cover the input prologue -- in the forward kernel and, when
+    the weight needs a gradient, in the weight-gradient kernel?"""
     want = _lib.FUSE_IN_NORM | (_lib.FUSE_IN_NORM_WGRAD if need_wgrad else 0)
-    return (have & want) == want
+    return not spec.up2 and (have & want) == want
+
+
+def _fusable_input(x, spec, scale, shift, res, need_wgrad):
+    """Can the conv (spec) stage the NormedInput x through its prologue?"""
+    p = _params(spec, x.shape, scale is not None, shift is not None, res is not None)
+    return _takes_prologue(spec, _lib.load().cfun_conv3d_fused_support(C.byref(p)), need_wgrad)
+
+
+def _conv(x, wp, w_src, spec, scale, shift, res, out, dx_slot, stats, shift_scaled=False):
+    """conv3d / conv3d_w: the conv's parameters and its fusion support, asked once, settle how a ``NormedInput`` x is read
+    (through the prologue, or materialised) and whether ``stats`` can be filled by the epilogue."""
+    p = _params(spec, x.shape, scale is not None, shift is not None, res is not None)
+    normed = isinstance(x, NormedInput)
+    have = _lib.load().cfun_conv3d_fused_support(C.byref(p)) if stats is not None or (normed and not spec.up2) else 0
+    pro = None
+    if normed and _takes_prologue(spec, have, (wp if w_src is None else w_src).requires_grad):
+        x, pro = x.token, x.pro()
+        if pro[0] is not None and tuple(pro[0].shape) != (p.N, p.Ci, 2):
+            raise RuntimeError("conv3d: input statistics %s do not fit x %s" % (tuple(pro[0].shape), tuple(x.shape)))
+    elif normed:
+        x = x.materialize()
+    if w_src is not None:
+        w_src = _tag_wgrad_stream(w_src, x)
+    call = _ConvCall(spec, p, out, dx_slot, stats if have & _lib.FUSE_OUT_STATS else None, pro, shift_scaled)
+    return _Conv3d.apply(x, wp, scale, shift, res, w_src, call)
 
 
 def conv3d(x, wp, spec, scale=None, shift=None, res=None, out=None, dx_slot=None, stats=None):
@@ -450,27 +471,15 @@ def conv3d(x, wp, spec, scale=None, shift=None, res=None, out=None, dx_slot=None
     (BatchBuffer, i) -- write y / the input gradient into sample i of a shared batch buffer (per-sample convs).
     ``stats``: a ``StatsSlot`` (or (slot, i) for per-sample convs) that receives y's InstanceNorm statistics.
     x may be a ``NormedInput``."""
-    pro = None
-    if isinstance(x, NormedInput):
-        if _fusable_input(x, spec, scale, shift, res, wp.requires_grad):
-            x, pro = x.token, x.pro()
-        else:
-            x = x.materialize()
-    return _Conv3d.apply(x, wp, scale, shift, res, spec, out, dx_slot, None, stats, pro)
+    return _conv(x, wp, None, spec, scale, shift, res, out, dx_slot, stats)
 
 
 def conv3d_w(x, w, spec, scale=None, shift=None, res=None, out=None, dx_slot=None, stats=None, shift_scaled=False):
     """``conv3d`` on an OIDHW weight [Co,Ci,kd,kh,kw] (a parameter, a gathered slice of one, a folded up-conv
     weight): packed inside the op, and the weight gradient is produced directly in OIDHW -- the reduction of the
-    wgrad kernel's per-chunk partial sums and the un-packing are one kernel (cfun_conv3d_bwd_weight_oidhw) instead
+    wgrad kernel's per-chunk partial sums and the un-packing are one kernel (cfun_conv3d_bwd_weight_fused, oidhw) instead
     of conv3d(x, pack_weight(w))'s reduce + un-pack launches.  Same values bit for bit."""
-    pro = None
-    if isinstance(x, NormedInput):
-        if _fusable_input(x, spec, scale, shift, res, w.requires_grad):
-            x, pro = x.token, x.pro()
-        else:
-            x = x.materialize()
-    return _Conv3d.apply(x, None, scale, shift, res, spec, out, dx_slot, _tag_wgrad_stream(w, x), stats, pro, shift_scaled)
+    return _conv(x, None, w, spec, scale, shift, res, out, dx_slot, stats, shift_scaled)
 
 
 # ---- zero-copy batch split / join (per-sample convs inside a batched graph) ------------------------------------
@@ -610,21 +619,14 @@ class _FC(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         x, w, scale, y = ctx.saved_tensors
-        need_x, need_w, need_scale, need_shift = ctx.needs_input_grad[:4]
+        need_x, need_w, need_scale, need_shift, _ = ctx.needs_input_grad
         if need_scale:
             raise RuntimeError("cfun_amd fc: gradient w.r.t. the epilogue scale is not implemented (frozen BatchNorm)")
         r, k = x.shape
         o = w.shape[0]
         dy = _c(dy)
         st = stream(dy)
-        gp = dy
-        if ctx.act != ACT_NONE:
-            gp = torch.empty_like(dy)
-            check(lib.cfun_act_bwd(ptr(y), ptr(dy), None, ptr(gp), r, o, 1, ctx.act, LRELU_SLOPE, 0, st), "act_bwd")
-        g = gp
-        if scale is not None:
-            g = torch.empty_like(dy)
-            check(lib.cfun_act_bwd(None, ptr(gp), ptr(scale), ptr(g), r, o, 1, ACT_NONE, LRELU_SLOPE, 1, st), "act_bwd(scale)")
+        gp, g = _grad_prep(lib, dy, y, scale, ctx.act, r, o, 1, 1, st)
         dx = dw = dshift = None
         if need_x:
             dx = torch.empty_like(x)
@@ -1045,8 +1047,6 @@ def nms3d(boxes, scores, threshold, max_num):
     return keep, count
 
 
-
-
 def resize3d(vol, out_dims, order=1, frame=None, offset=None, clip=False):
     """Resize a 3-D float volume (any strides: a permuted view of the loader's [H,W,D] array is read in place) to the
     dense ``out_dims`` with cfun_resize3d: order 1 = skimage.transform.resize(order=1, mode='constant') as evaluated
@@ -1085,8 +1085,6 @@ def halo_unpack(buf, x, z0):
     buf = _c(buf)                  # held across the launch (a temporary could be recycled before the kernel reads it)
     check(lib.cfun_halo_unpack(ptr(buf), ptr(x), n, d, h, w, c, z0, planes, stream(x)), "halo_unpack")
     return x
-
-
 
 
 def to_ndhwc(x):

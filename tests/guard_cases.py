@@ -1,13 +1,17 @@
 """Cases of the guard tier shared by test_guard_emu.py and test_guard_gpu.py: the zero-size contract of the wrappers, small
-cases for C entries no other kernel case reaches (plain torch references, in the style of kernel_cases.py), and the
+cases for C entries no other kernel case reaches (plain torch references, in the style of kernel_cases.py; the plain conv
+entries against the fused ones the wrappers call), and the
 accounting of the entries that ran under guard against ``_lib.EXPORTS``."""
+import ctypes as C
+
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 import guard
 from cfun_amd import _lib, ops
-from kernel_cases import _gen, assert_close, py_bounds, randn
+from cfun_amd._lib import ACT_LRELU, ALGO_DIRECT, ALGO_MFMA
+from kernel_cases import _gen, assert_close, py_bounds, randn, ref_conv
 from oracle import cfun_oracle as orc
 
 # Entries that need no run under guard, one reason each.  Everything else in _lib.EXPORTS launches work and must have been
@@ -33,6 +37,7 @@ def check_all(device):
     check_roi_align_whole_map_entries(device)
     check_mask_losses_bwd_entry(device)
     check_concat_lrelu(device)
+    check_plain_conv_entries(device)
 
 
 def check_concat_lrelu(device, seed=64):
@@ -148,6 +153,45 @@ def check_mask_losses_bwd_entry(device, seed=63):
         _lib.check(lib.cfun_mask_losses_bwd(ops.ptr(probs), ops.ptr(labd), ops.ptr(g), ops.ptr(g[1:]), ops.ptr(dl), n, d, h, w, c,
                                             ops.ptr(ws), ws.numel(), ops.stream(ld)), "mask_losses_bwd")
         assert_close(dl.permute(0, 4, 1, 2, 3), lr.grad, "cfun_mask_losses_bwd vs oracle (C=%d)" % c, 1e-3)
+
+
+def check_plain_conv_entries(device, seed=65):
+    """cfun_conv3d_fwd, cfun_conv3d_bwd_weight and cfun_conv3d_bwd_weight_oidhw (the plain entries of the C ABI; the wrappers
+    call cfun_conv3d_fwd_fused / cfun_conv3d_bwd_weight_fused for every conv, with a null fusion for a plain one) through the
+    C ABI: equal BIT FOR BIT to the fused entry with a null fusion on the same inputs, on an MFMA shape and a direct one; y and
+    the OIDHW gradient also against torch at kernel_cases.check_conv's bound."""
+    lib = _lib.load()
+    gen = _gen(seed)
+    for n, dhw, ci, co, algo in ((2, (4, 5, 7), 16, 16, ALGO_MFMA), (1, (4, 5, 6), 3, 8, ALGO_DIRECT)):
+        spec = ops.ConvSpec(k=(3, 3, 3), co=co, pad=(1, 1, 1), act=ACT_LRELU, algo=algo)
+        x, w = randn(gen, n, *dhw, ci), randn(gen, co, ci, 3, 3, 3) / float(27 * ci) ** 0.5
+        shift, g = randn(gen, co), randn(gen, n, *dhw, co)          # g: the gradient w.r.t. the conv sum
+        wr = w.clone().requires_grad_(True)
+        F.conv3d(x.permute(0, 4, 1, 2, 3), wr, padding=1).backward(g.permute(0, 4, 1, 2, 3))
+        xd, sd, gd = x.to(device), shift.to(device), g.to(device)
+        wp = ops.pack_weight(w.to(device))
+        p = ops._params(spec, xd.shape, False, True, False)
+        bp, st = C.byref(p), ops.stream(xd)
+        y = [torch.empty((n,) + dhw + (co,), dtype=torch.float32, device=device) for _ in range(2)]
+        ws = _lib.workspace(lib.cfun_conv3d_fwd_workspace_bytes(bp), xd)
+        _lib.check(lib.cfun_conv3d_fwd(ops.ptr(xd), ops.ptr(wp), None, ops.ptr(sd), None, ops.ptr(y[0]), bp, ops.ptr(ws),
+                                       ws.numel(), st), "conv3d_fwd")
+        ws = _lib.workspace(lib.cfun_conv3d_fwd_fused_workspace_bytes(bp, None), xd)
+        _lib.check(lib.cfun_conv3d_fwd_fused(ops.ptr(xd), ops.ptr(wp), None, ops.ptr(sd), None, ops.ptr(y[1]), bp, None,
+                                             ops.ptr(ws), ws.numel(), st), "conv3d_fwd_fused(null)")
+        assert torch.equal(y[0], y[1]), "cfun_conv3d_fwd differs from cfun_conv3d_fwd_fused with a null fusion (algo %d)" % algo
+        assert_close(y[0], ref_conv(x, w, spec, None, shift, None), "cfun_conv3d_fwd y (algo %d)" % algo)
+        for oidhw, plain in ((0, lib.cfun_conv3d_bwd_weight), (1, lib.cfun_conv3d_bwd_weight_oidhw)):
+            dw = [torch.empty(tuple(w.shape) if oidhw else tuple(wp.shape), dtype=torch.float32, device=device) for _ in range(2)]
+            ws = _lib.workspace(lib.cfun_conv3d_bwd_weight_workspace_bytes(bp), xd)
+            _lib.check(plain(ops.ptr(xd), ops.ptr(gd), ops.ptr(dw[0]), bp, ops.ptr(ws), ws.numel(), st), "conv3d_bwd_weight")
+            ws = _lib.workspace(lib.cfun_conv3d_bwd_weight_workspace_bytes(bp), xd)
+            _lib.check(lib.cfun_conv3d_bwd_weight_fused(ops.ptr(xd), ops.ptr(gd), ops.ptr(dw[1]), oidhw, bp, None, ops.ptr(ws),
+                                                        ws.numel(), st), "conv3d_bwd_weight_fused(null)")
+            assert torch.equal(dw[0], dw[1]), ("the plain weight-gradient entry differs from cfun_conv3d_bwd_weight_fused with a "
+                                               "null fusion (oidhw %d, algo %d)" % (oidhw, algo))
+            if oidhw:
+                assert_close(dw[0], wr.grad, "cfun_conv3d_bwd_weight_oidhw dw (algo %d)" % algo)
 
 
 def check_zero_size(device):
