@@ -91,7 +91,9 @@ def test_cfg2_full_size_step_properties(gpu, monkeypatch):
     """BASELINE.json configs[2] at FULL size (256x256x128, 'finetune', b = 20, 4 + 8 injected RoIs, 96^3 -> 192^3) --
     the step bench.py times: the heads are not skipped, all six losses and the gradients of all 95 trainable tensors are
     finite and non-zero, the step is bit-reproducible with fixed Dropout3d masks, and the value path (MFMA kernels)
-    agrees with the generic direct kernels (CFUN_CONV_ALGO=direct) on every loss to 1e-4 relative."""
+    agrees with the generic direct kernels (CFUN_CONV_ALGO=direct) on every loss to 1e-4 relative.  The tensors held here only
+    to finite / non-zero / reproducible (VERDICT.md weak spot 2) get their value check per layer: tests/test_product_shapes_gpu.py
+    replays every conv this step issues at its true shape against fp64."""
     from cfun_amd import config, step
     cfg = config.heart_config("finetune", 256, 256, 128)
     torch.manual_seed(0)

@@ -16,20 +16,23 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cfun_amd import _lib, ops  # noqa: E402
 from cfun_amd._lib import ACT_NONE, check, ptr  # noqa: E402
 
-# name, N, (D,H,W) of the stored input, Ci, Co, k, stride, mode   (mode: "", "up2", "fold3", "fold5")
+# name, N, (D,H,W) of the stored input, Ci, Co, k, stride, mode   (mode: "", "up2", "fold3", "fold5", "eval")
+# mode "": a conv the cfg2 training step issues in exactly this form (tests/test_product_shapes_gpu.py holds the table to the
+# recorded step); "eval": the dense batched form of a Dropout3d level, which only runs without dropout (inference) -- in
+# training those levels run as the per-RoI sparse-dropout pairs listed below; timed like the rest, left out of the sum
 B = 20
 LAYERS = [
     ("c1_1 stem 1->20 @96", 4, (96, 96, 96), 1, B, 3, 1, ""),
-    ("c1_2 / lrelu_conv_c1 20->20 @96", 4, (96, 96, 96), B, B, 3, 1, ""),
+    ("c1_2 / lrelu_conv_c1 20->20 @96", 4, (96, 96, 96), B, B, 3, 1, "eval"),
     ("l4.0 40->40 @96", 4, (96, 96, 96), 2 * B, 2 * B, 3, 1, ""),
     ("l3.3 up2 40->20 @48->96 (unfolded)", 4, (48, 48, 48), 2 * B, B, 3, 1, "up2"),
     ("l3.3 up2 40->20 @48->96 (folded)", 4, (48, 48, 48), 2 * B, B, 3, 1, "fold3"),
     ("c2 s2 20->40 @96->48", 4, (96, 96, 96), B, 2 * B, 3, 2, ""),
-    ("nlc_c2 40->40 @48", 4, (48, 48, 48), 2 * B, 2 * B, 3, 1, ""),
+    ("nlc_c2 40->40 @48", 4, (48, 48, 48), 2 * B, 2 * B, 3, 1, "eval"),
     ("l3.0 80->80 @48", 4, (48, 48, 48), 4 * B, 4 * B, 3, 1, ""),
     ("l2.3 up2 80->40 @24->48 (unfolded)", 4, (24, 24, 24), 4 * B, 2 * B, 3, 1, "up2"),
     ("l2.3 up2 80->40 @24->48 (folded)", 4, (24, 24, 24), 4 * B, 2 * B, 3, 1, "fold3"),
-    ("nlc_c3 80->80 @24", 4, (24, 24, 24), 4 * B, 4 * B, 3, 1, ""),
+    ("nlc_c3 80->80 @24", 4, (24, 24, 24), 4 * B, 4 * B, 3, 1, "eval"),
     ("l2.0 160->160 @24", 4, (24, 24, 24), 8 * B, 8 * B, 3, 1, ""),
     ("l1.3 up2 160->80 @12->24 (folded)", 4, (12, 12, 12), 8 * B, 4 * B, 3, 1, "fold3"),
     ("nlc_c4 160->160 @12", 4, (12, 12, 12), 8 * B, 8 * B, 3, 1, ""),
@@ -117,14 +120,15 @@ def main():
         t_f = timeit(lambda: check(lib.cfun_conv3d_fwd(ptr(x), ptr(wp), None, None, None, ptr(y), C.byref(p), ptr(ws_f), ws_f.numel(), st), "f"), args.iters)
         t_d = timeit(lambda: check(lib.cfun_conv3d_bwd_data(ptr(g), ptr(wpT), ptr(dx), C.byref(p), ptr(ws_d), ws_d.numel(), st), "d"), args.iters)
         t_w = timeit(lambda: check(lib.cfun_conv3d_bwd_weight(ptr(x), ptr(g), ptr(dwp), C.byref(p), ptr(ws_w), ws_w.numel(), st), "w"), args.iters)
-        for i, t in enumerate((t_f, t_d, t_w)):
-            tot[i] += t
+        if L[7] != "eval":      # the sum is over what the training step runs
+            for i, t in enumerate((t_f, t_d, t_w)):
+                tot[i] += t
         extra = ""
         if L[3] == 1:      # C_in = 1 stem: HBM-bound, algorithmic bytes = input + output + weights
             nbytes = 4.0 * (x.numel() + y.numel() + wp.numel())
             extra = "   fwd %.0f GB/s" % (nbytes / t_f / 1e6)
         print("%-44s %9.3f %9.3f %9.3f   %6.1f %6.1f %6.1f%s" % (L[0], t_f, t_d, t_w, flops / t_f / 1e9, flops / t_d / 1e9, flops / t_w / 1e9, extra))
-    print("%-44s %9.3f %9.3f %9.3f" % ("sum", *tot))
+    print("%-44s %9.3f %9.3f %9.3f" % ("sum (without the eval-only layers)", *tot))
 
 
 if __name__ == "__main__":
