@@ -146,6 +146,16 @@ _SIGNATURES = {
 
 EXPORTS = tuple(_SIGNATURES)
 
+# The training-sample entries (include/cfun_sample.h): the same shared object, a table of their own.  EXPORTS is tied to
+# cfun_hip.h and to the guard tier's coverage inside its own two files; these are checked by tests/test_sample_*.py.
+_D = C.c_double
+SAMPLE_SIGNATURES = {
+    "cfun_sample_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "cfun_sample_rotate_bbox": (C.c_int, [_P, _P, _P, _P, _P, _D, _D, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "cfun_sample_rpn_targets": (C.c_int, [_P, _I, _P, _I, _P, _I, _P, _D, _D, _P, _P, _P, _P, _Z, _P]),
+}
+SAMPLE_EXPORTS = tuple(SAMPLE_SIGNATURES)
+
 _lib = None
 _lib_path = None
 _is_emulator = False
@@ -166,7 +176,7 @@ def load():
             "cfun_amd: %s not found -- the HIP library is required (no CPU fallback). Build it with "
             "`make -C cfun_amd/csrc -j8` or `python -c 'import __graft_entry__ as g; g.build()'`." % path)
     lib = C.CDLL(path)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args

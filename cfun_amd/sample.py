@@ -1,0 +1,134 @@
+"""A training sample built on the device: the reference's ``load_image_gt`` (model.py:1007-1181; LiTS_2017/model.py:1010-1032).
+
+    rotate_and_box      per-slice nearest rotation of image and label, [H,W,D] -> [D,H,W], uint8 labels, utils.extract_bboxes'
+                        box and its 5 % expansion (model.py:1059-1075 / utils.extend_bbox)  -- cfun_sample_rotate_bbox
+    build_rpn_targets   model.build_rpn_targets (model.py:1090-1181)                         -- cfun_sample_rpn_targets
+    load_image_gt       both plus utils.mold_image and the class tiling: the dict ``train.train_epoch`` consumes
+    make_sample         utils.resize_image / resize_mask (mode 'self') in front of load_image_gt
+
+Nothing on this path waits for the device: box, tiling and counts stay device tensors.  Only ``strict=True`` reads back (the
+empty flag and the label range) and raises where the reference would.
+
+Two departures from the reference, both deliberate:
+  * its two ``np.random.choice`` draws are a deterministic contract here: among the positives the ``R // 2`` smallest in
+    (key, anchor index) order stay, among the negatives the ``R - positives_kept`` smallest; ``keys`` are uint32 per anchor
+    (``None``: drawn with torch.randint on the device);
+  * an empty label volume gives zero boxes and ``empty == 1`` instead of an exception.
+Not pinned by the reference: the rotation against imgaug's ``iaa.Affine(rotate, order=0)`` -- imgaug and its backends are not
+available to this project's environments.  The rule (cfun_sample.h) follows imgaug's documented construction: centre
+``size / 2 - 0.5``, nearest sample, constant 0 outside; exact half-voxel ties and cv2's fixed-point coordinates may differ by one
+voxel along edges.
+"""
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib, utils
+from ._lib import check, ptr, stream, workspace
+from .ops import ptr_raw
+
+NEG_IOU, POS_IOU = 0.3, 0.7          # model.py:1119,1126
+
+
+def _volume(image):
+    if image.dim() == 4 and image.shape[3] == 1:
+        image = image[..., 0]
+    if image.dim() != 3:
+        raise ValueError("sample: [H,W,D] (or [H,W,D,1]) volume expected, got %s" % (tuple(image.shape),))
+    return image
+
+
+def rotate_and_box(image, mask, angle, strict=False):
+    """image float32 / mask integer, both [H,W,D] with any strides (the loader's arrays, read in place), ``angle`` in degrees or
+    ``None`` (no rotation: the LiTS form, bit-identical to angle 0).  Returns (image [D,H,W] float32, labels [D,H,W] uint8,
+    raw_box int32[6], box int32[6], empty int32[1]) on the device.  Preconditions: equal shapes; label values in [0, 255]
+    (the range is verified only with ``strict``, which reads back)."""
+    lib = _lib.load()
+    image, mask = _volume(image), _volume(mask)
+    if tuple(image.shape) != tuple(mask.shape):
+        raise ValueError("rotate_and_box: image %s and mask %s differ in shape" % (tuple(image.shape), tuple(mask.shape)))
+    if image.device != mask.device:
+        raise ValueError("rotate_and_box: image and mask sit on different devices")
+    if mask.dtype.is_floating_point or mask.dtype == torch.bool:
+        raise ValueError("rotate_and_box: integer label volume expected, got %s" % (mask.dtype,))
+    if image.dtype != torch.float32:
+        image = image.to(torch.float32)
+    if mask.dtype != torch.int32:
+        mask = mask.to(torch.int32)
+    h, w, d = [int(v) for v in image.shape]
+    if min(h, w, d) <= 0 or h > 65535:
+        raise ValueError("rotate_and_box: unsupported extent %s" % ((h, w, d),))
+    if strict:
+        lo, hi = torch.aminmax(mask)
+        if int(lo) < 0 or int(hi) > 255:
+            raise ValueError("rotate_and_box: label values must lie in [0, 255], got [%d, %d]" % (int(lo), int(hi)))
+    rotate = angle is not None
+    rad = math.radians(float(angle)) if rotate else 0.0
+    ws = workspace(lib.cfun_sample_workspace_bytes(h, w, d, 0, 0), image)
+    out = torch.empty((d, h, w), dtype=torch.float32, device=image.device)
+    labels = torch.empty((d, h, w), dtype=torch.uint8, device=image.device)
+    small = torch.empty(16, dtype=torch.int32, device=image.device)
+    raw_box, box, empty = small[0:6], small[6:12], small[12:13]
+    i64, i32 = C.c_int64 * 3, C.c_int32 * 3
+    check(lib.cfun_sample_rotate_bbox(ptr_raw(image), i64(*image.stride()), ptr_raw(mask), i64(*mask.stride()), i32(h, w, d),
+                                      math.cos(rad), math.sin(rad), int(rotate), ptr(out), ptr(labels), ptr(raw_box), ptr(box),
+                                      ptr(empty), ptr(ws), ws.numel(), stream(image)), "sample_rotate_bbox")
+    if strict and int(empty):
+        raise ValueError("rotate_and_box: the label volume is empty (the reference's extract_bboxes raises here as well)")
+    return out, labels, raw_box, box, empty
+
+
+def build_rpn_targets(anchors, gt_boxes, config, keys=None):
+    """anchors [A,6] float32 on the device, gt_boxes [G,6] (same units) -> (rpn_match int32 [1,A,1], rpn_bbox float32 [1,R,6],
+    counts int32[2] = positives kept, negatives kept).  ``keys``: integer tensor [A] whose low 32 bits order the subsampling."""
+    lib = _lib.load()
+    if anchors.dim() != 2 or anchors.shape[1] != 6 or gt_boxes.dim() != 2 or gt_boxes.shape[1] != 6:
+        raise ValueError("build_rpn_targets: [A,6] anchors and [G,6] boxes expected")
+    a, g, r = int(anchors.shape[0]), int(gt_boxes.shape[0]), int(config.RPN_TRAIN_ANCHORS_PER_IMAGE)
+    dev = anchors.device
+    anchors = anchors.to(torch.float32).contiguous()
+    gt = gt_boxes.to(device=dev, dtype=torch.float32).contiguous()
+    if keys is None:
+        keys = torch.randint(0, 1 << 32, (a,), dtype=torch.int64, device=dev)
+    if keys.numel() != a or keys.dtype.is_floating_point:
+        raise ValueError("build_rpn_targets: one integer key per anchor expected")
+    keys = keys.to(device=dev).reshape(a).to(torch.int64).bitwise_and(0xFFFFFFFF).to(torch.int32).contiguous()   # the uint32's bits
+    std = (C.c_double * 6)(*[float(v) for v in config.RPN_BBOX_STD_DEV])
+    empty_call = a == 0 or g == 0
+    ws = workspace(lib.cfun_sample_workspace_bytes(0, 0, 0, a, g), anchors)
+    make = torch.zeros if empty_call else torch.empty          # (a zero-size call launches nothing and writes nothing)
+    rpn_match = make((1, a, 1), dtype=torch.int32, device=dev)
+    rpn_bbox = make((1, r, 6), dtype=torch.float32, device=dev)
+    counts = make(2, dtype=torch.int32, device=dev)
+    check(lib.cfun_sample_rpn_targets(ptr(anchors), a, ptr(gt), g, ptr(keys), r, std, NEG_IOU, POS_IOU, ptr(rpn_match),
+                                      ptr(rpn_bbox), ptr(counts), ptr(ws), ws.numel(), stream(anchors)), "sample_rpn_targets")
+    return rpn_match, rpn_bbox, counts
+
+
+def load_image_gt(image, mask, angle, config, anchors, keys=None, strict=False):
+    """model.load_image_gt on the device.  image / mask: the network-size [H,W,D] (or [H,W,D,1]) volumes; ``angle`` in degrees,
+    ``None`` = the LiTS form (no rotation).  Returns the dict ``train.train_epoch`` consumes -- ``image`` [1,1,D,H,W] after
+    utils.mold_image, ``gt_class_ids`` 1 .. NUM_CLASSES-1, ``gt_boxes`` the expanded box tiled NUM_CLASSES-1 times (float32
+    voxels, as step.training_step_full takes them), ``gt_labels`` uint8 [D,H,W], ``rpn_match`` [1,A,1], ``rpn_bbox_t`` [1,R,6] --
+    plus ``raw_box``, ``empty`` and ``rpn_counts``."""
+    img, labels, raw_box, box, empty = rotate_and_box(image, mask, angle, strict=strict)
+    dev = img.device
+    nfg = int(config.NUM_CLASSES) - 1
+    boxf = box.to(torch.float32)[None]
+    rpn_match, rpn_bbox, counts = build_rpn_targets(anchors.to(dev), boxf, config, keys)
+    return dict(image=utils.mold_image(img)[None, None], gt_class_ids=torch.arange(1, nfg + 1, device=dev),
+                gt_boxes=boxf.repeat(nfg, 1), gt_labels=labels, rpn_match=rpn_match, rpn_bbox_t=rpn_bbox,
+                raw_box=raw_box, empty=empty, rpn_counts=counts)
+
+
+def make_sample(image_hwd, mask_hwd, angle, config, anchors, keys=None, strict=False):
+    """The loader's [H,W,D] image and label volumes (numpy or tensors, any size) -> a training sample: utils.resize_image /
+    resize_mask (mode 'self') to the network size, then load_image_gt."""
+    dev = anchors.device
+    image = _volume(torch.as_tensor(image_hwd).to(dev))
+    mask = _volume(torch.as_tensor(mask_hwd).to(dev))
+    mx, mn = int(config.IMAGE_MAX_DIM), int(config.IMAGE_MIN_DIM)
+    image = utils.resize_image(image[..., None].to(torch.float32), min_dim=mn, max_dim=mx, mode="self", device=dev)[0]
+    mask = utils.resize_mask(mask, None, None, max_dim=mx, min_dim=mn, mode="self", device=dev)
+    return load_image_gt(image, mask, angle, config, anchors, keys=keys, strict=strict)

@@ -6,8 +6,9 @@
     train_epoch      MaskRCNN.train_epoch (model.py:1574-1676): per sample forward, six losses, weighted total, backward,
                      clip_grad_norm_(5.0); optimizer step + zero_grad every BATCH_SIZE samples; the epoch's mean losses
 
-Out of this path: the DataLoader, load_image_gt's augmentation and anchor targets -- a sample here is
-what they hand to ``predict``: image, GT class ids / boxes / label volume, rpn_match, rpn_bbox.
+Out of this path: the DataLoader.  A sample here is what load_image_gt hands to ``predict`` -- image,
+GT class ids / boxes / label volume, rpn_match, rpn_bbox -- and ``cfun_amd.sample.load_image_gt`` / ``make_sample`` build it on
+the device (rotation, GT box, RPN targets: cfun_amd/csrc/sample.hip).
 """
 import torch
 
