@@ -17,6 +17,8 @@ ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 ALGO_AUTO, ALGO_DIRECT, ALGO_MFMA = 0, 1, 2
 ALGO_WINO = 4    # every supported 3x3x3 stride-1 conv on the Winograd F(2,3)-along-x kernel (AUTO picks it per shape)
 ALGO_WINO2 = 5   # ... with y in the Winograd domain as well (forward / data gradient)
+# OR-ed into an algo: force the 4x4x16 / 4x8x8 output tile of the forward / data-gradient kernels for this call
+TILE_G16, TILE_G8 = 0x100, 0x200
 
 
 class ConvParams(C.Structure):
@@ -156,6 +158,12 @@ SAMPLE_SIGNATURES = {
 }
 SAMPLE_EXPORTS = tuple(SAMPLE_SIGNATURES)
 
+# The output-tile query (include/cfun_tile.h): a host-side query in a table of its own, for the same reason.
+TILE_SIGNATURES = {
+    "cfun_conv3d_fwd_tile": (C.c_int, [_PP, C.POINTER(C.c_int32)]),
+}
+TILE_EXPORTS = tuple(TILE_SIGNATURES)
+
 _lib = None
 _lib_path = None
 _is_emulator = False
@@ -176,7 +184,7 @@ def load():
             "cfun_amd: %s not found -- the HIP library is required (no CPU fallback). Build it with "
             "`make -C cfun_amd/csrc -j8` or `python -c 'import __graft_entry__ as g; g.build()'`." % path)
     lib = C.CDLL(path)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include "conv3d_mfma.h"
+#include "../../include/cfun_tile.h"
 
 // conv3d_direct.hip
 int cfun_conv_fwd_direct(const float*, const float*, const float*, const float*, const float*, float*,
@@ -26,6 +27,7 @@ int cfun_wino_s2d_dgrad_supported(const CfunConv3dParams*, const CfunConv3dParam
 int cfun_wino_fwd(const float*, const float*, int, int, const float*, const float*, const float*, float*,
                   const CfunConv3dParams*, void*, size_t, const cfun_mfma::ConvMode*, int, hipStream_t);
 int cfun_wino_is_2d(const CfunConv3dParams*);
+int cfun_wino_geom(const CfunConv3dParams*);
 int cfun_wino_stat_slots(const CfunConv3dParams*, size_t);
 // elementwise.hip: (mean, rstd) per (n, channel) from per-slot fp64 sums [N][slots][2][C]
 int cfun_stats_finalize(const double* part, float* stats, int N, int slots, int C, int64_t V, float eps, int slot_minor, hipStream_t st);
@@ -52,14 +54,21 @@ struct Shape {
   PlanFn plan;
   WgFn wgrad;
   int max_nsub;
+  FwdFn fwd8;        // the 4 x 8 x 8 output tile (G8) of the forward / data-gradient kernel, or null
+  FwdWsFn fwd_ws8;
 };
 
 #define SHAPE(NAME, KD, KH, KW, S, MAXN) \
-  { KD, KH, KW, S, cfun_mfma_fwd_##NAME, cfun_mfma_fwd_ws_##NAME, cfun_mfma_wgrad_plan_##NAME, cfun_mfma_wgrad_##NAME, MAXN }
+  { KD, KH, KW, S, cfun_mfma_fwd_##NAME, cfun_mfma_fwd_ws_##NAME, cfun_mfma_wgrad_plan_##NAME, cfun_mfma_wgrad_##NAME, MAXN, \
+    nullptr, nullptr }
+#define SHAPE_G8(NAME, KD, KH, KW, S, MAXN) \
+  { KD, KH, KW, S, cfun_mfma_fwd_##NAME, cfun_mfma_fwd_ws_##NAME, cfun_mfma_wgrad_plan_##NAME, cfun_mfma_wgrad_##NAME, MAXN, \
+    cfun_mfma_fwd_g8_##NAME, cfun_mfma_fwd_ws_g8_##NAME }
+// G8 where the deep U-Net levels (24^3, 6^3) run: 3x3x3 stride 1 / 2 and the folded stride-2 data gradient (2x2x2)
 const Shape kShapes[] = {
-    SHAPE(k333s1, 3, 3, 3, 1, 5), SHAPE(k333s2, 3, 3, 3, 2, 5), SHAPE(k111s1, 1, 1, 1, 1, 5),
+    SHAPE_G8(k333s1, 3, 3, 3, 1, 5), SHAPE_G8(k333s2, 3, 3, 3, 2, 5), SHAPE(k111s1, 1, 1, 1, 1, 5),
     SHAPE(k111s2, 1, 1, 1, 2, 5), SHAPE(k133s1, 1, 3, 3, 1, 5), SHAPE(k311s1, 3, 1, 1, 1, 5),
-    SHAPE(k555s1, 5, 5, 5, 1, 1), SHAPE(k222s1, 2, 2, 2, 1, 5),
+    SHAPE(k555s1, 5, 5, 5, 1, 1), SHAPE_G8(k222s1, 2, 2, 2, 1, 5),
 };
 
 const Shape* find_shape(int kd, int kh, int kw, int s) {
@@ -127,6 +136,28 @@ const Shape* mfma_shape(const CfunConv3dParams* p) {
   return s;
 }
 
+// ---- output-tile geometry of the forward / data-gradient kernels (k_conv_mfma and k_conv_wino): G16 = 4(z) x 4(y) x 16(x)
+// or G8 = 4 x 8 x 8.  ONE rule for both families: G8 exactly when it strictly raises the filled fraction
+//   D*H*W / (ceil(D/TD)*TD * ceil(H/TH)*TH * ceil(W/TW)*TW)
+// of the tiled grid (the conv's output grid; the low-resolution grid of a depth-to-space / folded conv) and the kernel has
+// a G8 instantiation.  TD = 4 for both, so the z factor cancels.  H = W = 24: 24*32 -> 24*24 (0.75 -> 1.0); 6: 8*16 -> 8*8
+// (with z, 6 of 8: 0.21 -> 0.42); 20: 20*32 -> 24*24; 12: 12*16 -> 16*16, worse; 16, 32, 48, 96 and 16 x 32 x 32: equal -> G16.
+// CFUN_TILE_GEOM=auto|16|8 overrides the rule for the process, CFUN_ALGO_TILE_G16 / _G8 in p->algo for one call.
+int tile_geom_knob() {
+  static int v = -2;      // A/B knob (tools/bench_layers.py)
+  if (v == -2) {
+    const char* e = getenv("CFUN_TILE_GEOM");
+    v = !e ? -1 : atoi(e) == 16 ? 0 : atoi(e) == 8 ? 1 : -1;
+  }
+  return v;
+}
+
+bool tile_geom_rule(const CfunConv3dParams* p) {
+  using cfun_mfma::cdiv;
+  const int64_t g16 = (int64_t)cdiv(p->Ho, 4) * 4 * cdiv(p->Wo, 16) * 16, g8 = (int64_t)cdiv(p->Ho, 8) * 8 * cdiv(p->Wo, 8) * 8;
+  return g8 < g16;
+}
+
 // the data gradient of a stride-1 conv is a stride-1 conv of g with flipped, transposed weights
 bool make_dgrad_params(const CfunConv3dParams* p, CfunConv3dParams* q) {
   if (p->stride != 1 || !standard_dims(p)) return false;
@@ -146,7 +177,7 @@ bool make_dgrad_params(const CfunConv3dParams* p, CfunConv3dParams* q) {
 // depth-to-space epilogue:  dx[2z+p] = sum_{a in {0,1}} g[z+a] * W[t(p,a)],  t(0,0)=1, t(1,0)=2, t(1,1)=0,
 // (0,1) -> no tap.  Folded weights wd[tap'=(a,b,c)][co][(pz,py,px)*Ci + ci] are built on device from wpT.
 bool use_folded_s2_dgrad(const CfunConv3dParams* p) {
-  return p->algo != CFUN_ALGO_DIRECT && p->stride == 2 && !p->up2 && p->kd == 3 && p->kh == 3 && p->kw == 3 &&
+  return CFUN_ALGO_OF(p->algo) != CFUN_ALGO_DIRECT && p->stride == 2 && !p->up2 && p->kd == 3 && p->kh == 3 && p->kw == 3 &&
          p->pd == 1 && p->ph == 1 && p->pw == 1 && !((p->Di | p->Hi | p->Wi) & 1) && !(p->Ci & 3) && !(p->Co & 3) &&
          p->Di == 2 * p->Do && p->Hi == 2 * p->Ho && p->Wi == 2 * p->Wo;
 }
@@ -206,7 +237,7 @@ int wgrad_nsub(const CfunConv3dParams* p, const Shape* s) {
 }
 
 bool use_mfma_dgrad(const CfunConv3dParams* p, CfunConv3dParams* q, const Shape** s) {
-  if (p->algo == CFUN_ALGO_DIRECT) return false;
+  if (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT) return false;
   if (!make_dgrad_params(p, q)) return false;
   *s = mfma_shape(q);
   return *s != nullptr;
@@ -338,6 +369,14 @@ int splitk_stats_blocks(const CfunConv3dParams* p, int* lanes_out) {
 
 int cfun_splitk_stat_slots(const CfunConv3dParams* p) { return splitk_stats_blocks(p, nullptr); }
 
+// g8_exists: 0 no G8 instantiation, 1 one that the rule may pick, 2 one that only an override picks (g8_loses_wave)
+int cfun_tile_geom(const CfunConv3dParams* p, int g8_exists) {
+  if (!g8_exists || (p->algo & CFUN_ALGO_TILE_G16)) return 0;
+  if (p->algo & CFUN_ALGO_TILE_G8) return 1;
+  if (tile_geom_knob() >= 0) return tile_geom_knob();
+  return g8_exists == 1 && tile_geom_rule(p) ? 1 : 0;
+}
+
 int cfun_splitk_finish(const float* partial, int ksplit, const float* scale, const float* shift, const float* res,
                        float* y, const CfunConv3dParams* p, double* stat_part, hipStream_t st) {
   if (stat_part) {
@@ -395,23 +434,72 @@ static void fwd_mode(const CfunConv3dParams* p, const Shape* s, ConvMode* md, in
   }
 }
 
+// geometry of the k_conv_mfma launch (shape s, mode md, tile code nsub) of conv p.  No G8 copy exists of the s2d gather
+// without tap skipping (MODE 1) and of the 40-channel remainder tile.
+// G8 twins that keep fewer workgroups resident per CU than their G16 instantiation -- by registers (tools/kernel_regs.sh:
+// the two rows of a G8 M-subtile share fewer halo reads between taps, +3 ... +10 VGPRs) or by LDS (the padded halo rows: the
+// stride-2 tile is 58.8 KB against 42.8 KB).  The rule leaves them on G16; an override still runs them (the small test
+// shapes of tests/tile_geometry_cases.py do).  A tile code is listed when EITHER of its two instantiations (with / without the
+// statistics epilogue) loses a wave.  No conv of the training step lands on a listed tile.  Table:
+// profiles/tile_geom_kernel_regs.txt.  (tile code nsub = NSUB + 8 * REM)
+static bool g8_loses_wave(const Shape* s, const ConvMode& md, int nsub) {
+  if (s->kd == 2) return nsub == 1;                                        // 8 -> 7 waves per SIMD
+  if (s->s == 2) return nsub == 1 || nsub == 4 || nsub == 0 + 8 * 2;       // LDS: 3 -> 2, 2 -> 1, 3 -> 2 workgroups
+  if (md.tap_skip == 1 || md.in_s2d) return false;      // folded up-conv, forward (conv_min_waves) and data gradient: none
+  return nsub == 3 || nsub == 4 || nsub == 5 || nsub == 1 + 8 * 1;         // plain 3x3x3: 3 -> 2, 3 -> 2, 2 -> 1, 4 -> 3
+}
+
+// Launches the rule would switch but G8 measured no faster on (tools/bench_layers.py, CFUN_TILE_GEOM=16 | 8 | 16 | 8 in one
+// call, ms; profiles/tile_geom_layers.log): at 6^3 a launch without split-K has 128 instead of 256 workgroups of the same
+// length for 256 CUs --
+//   l0.3 folded up-conv 320 -> 160 @ 4 x 6^3, forward:      0.260 / 0.258 -> 0.260 / 0.260   (its data gradient: 0.240 -> 0.136, kept)
+//   c5 3x3x3 stride 2 160 -> 320 @ 4 x 12^3 -> 6^3, folded 2x2x2 data gradient:  0.238 / 0.236 -> 0.239 / 0.239   (forward 0.114 -> 0.098, kept)
+static bool g8_no_gain(const CfunConv3dParams* p, const Shape* s, const ConvMode& md) {
+  return (s->kd == 2 || md.tap_skip == 1) && (int64_t)p->Do * p->Ho * p->Wo <= 6 * 6 * 6;
+}
+
+static int mfma_geom(const CfunConv3dParams* p, const Shape* s, const ConvMode& md, int nsub) {
+  const bool has = s->fwd8 && nsub != 2 + 8 * 2 && (!md.in_s2d || (md.tap_skip == 2 && nsub < 8));
+  return cfun_tile_geom(p, !has ? 0 : (g8_loses_wave(s, md, nsub) || g8_no_gain(p, s, md)) ? 2 : 1);
+}
+
 size_t cfun_conv3d_fwd_workspace_bytes(const CfunConv3dParams* p) {
   if (!valid_params(p)) return 0;
-  const Shape* s = p->algo == CFUN_ALGO_DIRECT ? nullptr : mfma_shape(p);
+  const Shape* s = CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT ? nullptr : mfma_shape(p);
   if (!s) return 256;
   ConvMode md;
   int nsub;
   fwd_mode(p, s, &md, &nsub);
-  size_t need = s->fwd_ws(nsub, *p, md);
+  size_t need = (mfma_geom(p, s, md, nsub) ? s->fwd_ws8 : s->fwd_ws)(nsub, *p, md);
   if (cfun_wino_supported(p) && cfun_wino_workspace_bytes(p) > need) need = cfun_wino_workspace_bytes(p);
   return cfun_align_up(need + 256, 256);
 }
 
+int cfun_conv3d_fwd_kernel(const CfunConv3dParams* p);
+
+int cfun_conv3d_fwd_tile(const CfunConv3dParams* p, int32_t out[3]) {
+  if (!out || !valid_params(p)) return CFUN_EINVAL;
+  const int k = cfun_conv3d_fwd_kernel(p);
+  if (k != CFUN_KERNEL_MFMA && k != CFUN_KERNEL_WINO) return CFUN_EINVAL;
+  int g;
+  if (k == CFUN_KERNEL_WINO) {
+    g = cfun_wino_geom(p);
+  } else {
+    ConvMode md;
+    int nsub;
+    const Shape* s = mfma_shape(p);
+    fwd_mode(p, s, &md, &nsub);
+    g = mfma_geom(p, s, md, nsub);
+  }
+  out[0] = 4; out[1] = g ? 8 : 4; out[2] = g ? 8 : 16;
+  return CFUN_OK;
+}
+
 int cfun_conv3d_fwd_kernel(const CfunConv3dParams* p) {
   if (!valid_params(p)) return CFUN_EINVAL;
-  if (p->algo == CFUN_ALGO_AUTO && cfun_conv_pointwise_supported(p)) return CFUN_KERNEL_POINTWISE;
-  if (p->algo != CFUN_ALGO_DIRECT && mfma_shape(p)) return cfun_wino_supported(p) ? CFUN_KERNEL_WINO : CFUN_KERNEL_MFMA;
-  if (p->algo != CFUN_ALGO_DIRECT && p->algo != CFUN_ALGO_MFMA && cfun_conv_stem_supported(p)) return CFUN_KERNEL_STEM;
+  if (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_AUTO && cfun_conv_pointwise_supported(p)) return CFUN_KERNEL_POINTWISE;
+  if (CFUN_ALGO_OF(p->algo) != CFUN_ALGO_DIRECT && mfma_shape(p)) return cfun_wino_supported(p) ? CFUN_KERNEL_WINO : CFUN_KERNEL_MFMA;
+  if (CFUN_ALGO_OF(p->algo) != CFUN_ALGO_DIRECT && CFUN_ALGO_OF(p->algo) != CFUN_ALGO_MFMA && cfun_conv_stem_supported(p)) return CFUN_KERNEL_STEM;
   return CFUN_KERNEL_DIRECT;
 }
 
@@ -423,12 +511,12 @@ static int conv_fwd_impl(const float* x, const float* wp, const float* scale, co
   if ((p->scale_mode && !scale) || (p->has_shift && !shift) || (p->res_mode && !res)) return CFUN_EINVAL;
   if (p->scale_mode < 0 || p->scale_mode > 2 || p->res_mode < 0 || p->res_mode > 1) return CFUN_EINVAL;
   const bool fused = fz && (fz->in_stats || fz->in_act || fz->out_part);
-  if (p->algo == CFUN_ALGO_AUTO && cfun_conv_pointwise_supported(p) && cfun_aligned16(x) && cfun_aligned16(y)) {
+  if (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_AUTO && cfun_conv_pointwise_supported(p) && cfun_aligned16(x) && cfun_aligned16(y)) {
     if (fused && (fz->out_part || !cfun_conv_pointwise_in_supported(p))) return CFUN_EINVAL;
     return cfun_conv_pointwise_fwd(x, wp, scale, shift, res, y, p, fused ? fz->in_stats : nullptr, fused ? fz->in_act : 0,
                                    fused ? fz->in_slope : 0.f, cfun_st(stream));   // 1x1x1 -> 8: streaming
   }
-  const Shape* s = p->algo == CFUN_ALGO_DIRECT ? nullptr : mfma_shape(p);
+  const Shape* s = CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT ? nullptr : mfma_shape(p);
   if (s) {
     if (!cfun_aligned16(x) || !cfun_aligned16(wp) || !cfun_aligned16(y) || (scale && !cfun_aligned16(scale)) ||
         (shift && !cfun_aligned16(shift)) || (res && !cfun_aligned16(res)))
@@ -445,12 +533,13 @@ static int conv_fwd_impl(const float* x, const float* wp, const float* scale, co
       return cfun_wino_fwd(x, wp, 0, 0, scale, shift, res, y, p, ws, ws_bytes, &md, prepared, cfun_st(stream));
     }
     if (prepared && cfun_wino_supported(p)) return CFUN_EWORKSPACE;      // wp is the Winograd operand: no plain kernel can read it
-    if (stat_slots) *stat_slots = cfun_mfma::fwd_stat_slots(nsub, *p, md, ws ? ws_bytes : 0);
-    return s->fwd(nsub, x, wp, scale, shift, res, y, *p, md, ws, ws ? ws_bytes : 0, cfun_st(stream));
+    const int geom = mfma_geom(p, s, md, nsub);
+    if (stat_slots) *stat_slots = cfun_mfma::fwd_stat_slots(nsub, geom, *p, md, ws ? ws_bytes : 0);
+    return (geom ? s->fwd8 : s->fwd)(nsub, x, wp, scale, shift, res, y, *p, md, ws, ws ? ws_bytes : 0, cfun_st(stream));
   }
   if (fused) return CFUN_EINVAL;      // the fusion hooks live in the MFMA / Winograd kernels (cfun_conv3d_fused_support)
-  if (p->algo == CFUN_ALGO_MFMA) return CFUN_EINVAL;
-  if (p->algo != CFUN_ALGO_DIRECT && cfun_conv_stem_supported(p) && cfun_aligned16(y))
+  if (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_MFMA) return CFUN_EINVAL;
+  if (CFUN_ALGO_OF(p->algo) != CFUN_ALGO_DIRECT && cfun_conv_stem_supported(p) && cfun_aligned16(y))
     return cfun_conv_stem_fwd(x, wp, scale, shift, y, p, cfun_st(stream));    // C_in = 1: LDS-tiled, write-bound
   return cfun_conv_fwd_direct(x, wp, scale, shift, res, y, p, cfun_st(stream));
 }
@@ -464,9 +553,9 @@ int cfun_conv3d_fwd(const float* x, const float* wp, const float* scale, const f
 static bool wgrad_takes_prologue(const CfunConv3dParams* p);
 
 int cfun_conv3d_fused_support(const CfunConv3dParams* p) {
-  if (!valid_params(p) || p->algo == CFUN_ALGO_DIRECT || !mfma_shape(p)) return 0;
+  if (!valid_params(p) || CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT || !mfma_shape(p)) return 0;
   const int wg = wgrad_takes_prologue(p) ? CFUN_FUSE_IN_NORM_WGRAD : 0;
-  if (p->algo == CFUN_ALGO_AUTO && cfun_conv_pointwise_supported(p))      // the streaming 1x1x1 -> 8 kernel: prologue only
+  if (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_AUTO && cfun_conv_pointwise_supported(p))      // the streaming 1x1x1 -> 8 kernel: prologue only
     return cfun_conv_pointwise_in_supported(p) ? (CFUN_FUSE_IN_NORM | wg) : 0;
   const int st = (p->Co >> 2) <= 256 ? CFUN_FUSE_OUT_STATS : 0;           // (the split-K statistic finish: one thread per channel quad)
   if (cfun_wino_supported(p)) return st;                                  // k_conv_wino: epilogue statistics only
@@ -474,7 +563,9 @@ int cfun_conv3d_fused_support(const CfunConv3dParams* p) {
 }
 
 static size_t stat_part_bytes(const CfunConv3dParams* p) {
-  const int tiles = cfun_mfma::cdiv(p->Do, 4) * cfun_mfma::cdiv(p->Ho, 4) * cfun_mfma::cdiv(p->Wo, 16) * (p->d2s ? 8 : 1);
+  using cfun_mfma::cdiv;      // slots: one per tile of either geometry, or the split-K finish's blocks
+  const int t16 = cdiv(p->Do, 4) * cdiv(p->Ho, 4) * cdiv(p->Wo, 16), t8 = cdiv(p->Do, 4) * cdiv(p->Ho, 8) * cdiv(p->Wo, 8);
+  const int tiles = (t16 > t8 ? t16 : t8) * (p->d2s ? 8 : 1);
   const int sk = cfun_splitk_stat_slots(p);
   const int cy = p->d2s ? (p->d2s_cq > 0 ? p->d2s_cq : (p->Co >> 3)) : p->Co;
   return cfun_align_up((size_t)p->N * (tiles > sk ? tiles : sk) * 2 * cy * sizeof(double), 256);
@@ -524,8 +615,8 @@ int cfun_weight_prepare_kinds(const CfunConv3dParams* p, int32_t kinds[2], size_
   if (T > 27) return CFUN_OK;
   kinds[0] = CFUN_WOP_PACK;
   bytes[0] = (size_t)T * p->Ci * p->CoP * sizeof(float);
-  const bool pointwise = p->algo == CFUN_ALGO_AUTO && cfun_conv_pointwise_supported(p);
-  if (!pointwise && p->algo != CFUN_ALGO_DIRECT && mfma_shape(p) && cfun_wino_supported(p)) {
+  const bool pointwise = CFUN_ALGO_OF(p->algo) == CFUN_ALGO_AUTO && cfun_conv_pointwise_supported(p);
+  if (!pointwise && CFUN_ALGO_OF(p->algo) != CFUN_ALGO_DIRECT && mfma_shape(p) && cfun_wino_supported(p)) {
     const int twod = cfun_wino_is_2d(p);
     kinds[0] = twod ? CFUN_WOP_WINO2 : CFUN_WOP_WINO1;
     bytes[0] = (size_t)(twod ? 48 : 36) * p->Ci * p->CoP * sizeof(float);
@@ -556,7 +647,9 @@ size_t cfun_conv3d_bwd_data_workspace_bytes(const CfunConv3dParams* p) {
     ConvMode md = kPlain;
     md.flip = 1;
     if (p->d2s) { md.in_s2d = 1; md.in_cqp = p->Co >> 3; md.in_cq = p->d2s_cq > 0 ? p->d2s_cq : md.in_cqp; }
-    size_t need = s->fwd_ws(pick_tile(s, q.Co, false), q, md);   // split-K partials
+    const int nsub = pick_tile(s, q.Co, false);
+    if (p->d2s) md.tap_skip = p->tap_skip ? 2 : 0;
+    size_t need = (mfma_geom(&q, s, md, nsub) ? s->fwd_ws8 : s->fwd_ws)(nsub, q, md);   // split-K partials
     if ((p->d2s ? cfun_wino_s2d_dgrad_supported(p, &q) : cfun_wino_supported(&q)) && cfun_wino_workspace_bytes(&q) > need)
       need = cfun_wino_workspace_bytes(&q);
     return cfun_align_up(need + 256, 256);
@@ -583,7 +676,9 @@ int cfun_conv3d_bwd_data(const float* g, const float* wpT, float* dx, const Cfun
       wd = (const float*)ws;
     }
     const Shape* s2 = find_shape(2, 2, 2, 1);
-    return s2->fwd(pick_nsub(q.Co, s2->max_nsub), g, wd, nullptr, nullptr, nullptr, dx, q, kPlain, nullptr, 0, cfun_st(stream));
+    const int nsub = pick_nsub(q.Co, s2->max_nsub);
+    return (mfma_geom(&q, s2, kPlain, nsub) ? s2->fwd8 : s2->fwd)(nsub, g, wd, nullptr, nullptr, nullptr, dx, q, kPlain, nullptr, 0,
+                                                                   cfun_st(stream));
   }
   if (use_mfma_dgrad(p, &q, &s)) {
     if (!cfun_aligned16(g) || !cfun_aligned16(wpT) || !cfun_aligned16(dx)) return CFUN_EALIGN;
@@ -601,9 +696,10 @@ int cfun_conv3d_bwd_data(const float* g, const float* wpT, float* dx, const Cfun
       return cfun_wino_fwd(g, wpT, 1, p->d2s ? (p->Co >> 3) : 0, nullptr, nullptr, nullptr, dx, &q, ws, ws_bytes, nullptr,
                            prepared, cfun_st(stream));
     if (wino && prepared) return CFUN_EWORKSPACE;       // wpT is the Winograd operand
-    if (!p->up2) return s->fwd(nsub, g, wpT, nullptr, nullptr, nullptr, dx, q, md, ws, cfun_aligned16(ws) ? ws_bytes : 0, cfun_st(stream));
+    const FwdFn fwd = mfma_geom(&q, s, md, nsub) ? s->fwd8 : s->fwd;
+    if (!p->up2) return fwd(nsub, g, wpT, nullptr, nullptr, nullptr, dx, q, md, ws, cfun_aligned16(ws) ? ws_bytes : 0, cfun_st(stream));
     if (ws_bytes < cfun_conv3d_bwd_data_workspace_bytes(p) || !cfun_aligned16(ws)) return CFUN_EWORKSPACE;
-    const int rc = s->fwd(nsub, g, wpT, nullptr, nullptr, nullptr, (float*)ws, q, md, nullptr, 0, cfun_st(stream));
+    const int rc = fwd(nsub, g, wpT, nullptr, nullptr, nullptr, (float*)ws, q, md, nullptr, 0, cfun_st(stream));
     if (rc) return rc;
     return cfun_upsample2_bwd((const float*)ws, dx, p->N, p->Di, p->Hi, p->Wi, p->Ci, stream);
   }
@@ -620,8 +716,8 @@ static bool wgrad_mfma_fits(const CfunConv3dParams* p) {
 
 size_t cfun_conv3d_bwd_weight_workspace_bytes(const CfunConv3dParams* p) {
   if (!valid_params(p)) return 0;
-  if (p->algo != CFUN_ALGO_DIRECT && cfun_wgrad_c1_supported(p)) return cfun_align_up(cfun_wgrad_c1_ws(p), 256);
-  const Shape* s = (p->algo == CFUN_ALGO_DIRECT || !wgrad_mfma_fits(p)) ? nullptr : mfma_shape(p);
+  if (CFUN_ALGO_OF(p->algo) != CFUN_ALGO_DIRECT && cfun_wgrad_c1_supported(p)) return cfun_align_up(cfun_wgrad_c1_ws(p), 256);
+  const Shape* s = (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT || !wgrad_mfma_fits(p)) ? nullptr : mfma_shape(p);
   if (s && cfun_wino_wgrad_supported(p)) return cfun_align_up(cfun_wino_wgrad_workspace_bytes(p), 256);
   if (s) {
     cfun_mfma::WgPlan w;
@@ -632,7 +728,7 @@ size_t cfun_conv3d_bwd_weight_workspace_bytes(const CfunConv3dParams* p) {
 }
 
 static bool wgrad_takes_prologue(const CfunConv3dParams* p) {
-  if (p->algo == CFUN_ALGO_DIRECT || !wgrad_mfma_fits(p) || !mfma_shape(p)) return false;
+  if (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT || !wgrad_mfma_fits(p) || !mfma_shape(p)) return false;
   return !cfun_wgrad_c1_supported(p) && !cfun_wino_wgrad_supported(p);
 }
 
@@ -641,11 +737,11 @@ static int bwd_weight_any(const float* x, const float* g, CfunWgradDst dst, cons
   if (!valid_params(p)) return CFUN_EINVAL;
   const bool pro = f && (f->in_stats || f->in_act);
   if (pro && !wgrad_takes_prologue(p)) return CFUN_EINVAL;
-  if (p->algo != CFUN_ALGO_DIRECT && cfun_wgrad_c1_supported(p) && (int64_t)p->N * p->Do * p->Ho * p->Wo > 0) {
+  if (CFUN_ALGO_OF(p->algo) != CFUN_ALGO_DIRECT && cfun_wgrad_c1_supported(p) && (int64_t)p->N * p->Do * p->Ho * p->Wo > 0) {
     if (!cfun_aligned16(g) || !cfun_aligned16(ws)) return CFUN_EALIGN;
     return cfun_wgrad_c1(x, g, dst, p, ws, ws_bytes, cfun_st(stream));
   }
-  const Shape* s = (p->algo == CFUN_ALGO_DIRECT || !wgrad_mfma_fits(p)) ? nullptr : mfma_shape(p);
+  const Shape* s = (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT || !wgrad_mfma_fits(p)) ? nullptr : mfma_shape(p);
   if (s) {
     if (!cfun_aligned16(x) || !cfun_aligned16(g)) return CFUN_EALIGN;
     if (ws_bytes < cfun_conv3d_bwd_weight_workspace_bytes(p)) return CFUN_EWORKSPACE;
@@ -667,7 +763,7 @@ static int bwd_weight_any(const float* x, const float* g, CfunWgradDst dst, cons
     if (rc) return rc;
     return cfun_wgrad_finish((const float*)ws, dst, p, w.nchunks * w.kslots, cfun_st(stream));
   }
-  if (p->algo == CFUN_ALGO_MFMA) return CFUN_EINVAL;
+  if (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_MFMA) return CFUN_EINVAL;
   return cfun_conv_bwd_weight_direct(x, g, dst, p, ws, ws_bytes, cfun_st(stream));
 }
 

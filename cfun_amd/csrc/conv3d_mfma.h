@@ -2,8 +2,9 @@
 // (v_mfma_f32_16x16x4_f32: exact fp32, same rate as the fp32 vector peak but one VGPR per operand).
 //
 //   forward / data-gradient kernel (k_conv_mfma):
-//     block  = 256 threads (4 waves) -> 4(z) x 4(y) x 16(x) output voxels x (16*NSUB) output channels
-//     wave w = z-plane w of the tile; 4 m-subtiles (rows y) of 16 voxels along x
+//     block  = 256 threads (4 waves) -> 4(z) x 4(y) x 16(x) output voxels x (16*NSUB) output channels, or 4 x 8 x 8 (FwdTile's
+//              G = 1, "G8": the levels whose extent 16-wide tiles fill badly -- 24, 6; selection: conv3d.hip)
+//     wave w = z-plane w of the tile; 4 m-subtiles of 16 voxels: a row of 16 along x (G8: two rows of 8)
 //     K loop = input channels in chunks of 4 (one MFMA k-step) x all taps, operands from LDS:
 //       X tile   [4 ch][IZ*IY*IX voxels incl. halo]   (channel planes padded so that a wave's 4x16
 //                                                       fragment read is bank-conflict free)
@@ -33,7 +34,11 @@ int cfun_splitk_stat_slots(const CfunConv3dParams* p);
 
 namespace cfun_mfma {
 
-constexpr int pad_plane(int v, int rs) { return rs == 1 ? v + ((16 - (v % 32)) + 32) % 32 : (v | 1); }
+// channel-plane stride of the staged halo tile.  A fragment read is a ds_read_b32: two 32-lane groups (k = 0,1 | 2,3), banks
+// = dword address mod 32, so the 16 voxels of k and the 16 of k + 1 must cover the 32 banks exactly once.
+//   stride 1: the 16 voxels are 16 consecutive dwords (G16), or 8 + 8 one padded row (16 dwords) apart (G8)  ->  the next
+//             plane sits 16 (G16) / 8 (G8) banks further;   stride 2: the voxels take every other bank -> an odd plane
+constexpr int pad_plane(int v, int rs, int g = 0) { return rs != 1 ? (v | 1) : v + (((g ? 8 : 16) - (v % 32)) + 32) % 32; }
 constexpr int pad_row16(int v) { return (v % 32 == 16) ? v : v + 16; }  // v is a multiple of 16
 constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 // LDS row stride (floats) of a weight / gradient row of nt channels: = 16 (mod 32) so that the four k-rows of an
@@ -113,7 +118,7 @@ __device__ __forceinline__ void quad_park_16(const float (&sa)[4], const float (
   *reinterpret_cast<float4*>(r) = make_float4(sa[0], sb[0], sa[1], sb[1]);
   *reinterpret_cast<float4*>(r + 4) = make_float4(sa[2], sb[2], sa[3], sb[3]);
 }
-// all 64 lanes share the quad (remainder quads: lane = voxel (row lane>>4, x = lane&15)): the 4 rows are added first
+// all 64 lanes share the quad (remainder quads: lane = one voxel of the wave's plane): lanes l, l+16, l+32, l+48 are added first
 __device__ __forceinline__ void quad_park_wave(const float (&sa)[4], const float (&sb)[4], float* red, int es, int wv, int lane, int cl) {
   float u[4], v[4];
 #pragma unroll
@@ -166,9 +171,12 @@ __device__ __forceinline__ unsigned parity_tapmask(int q, bool flip) {
   return m;
 }
 
-template <int KD, int KH, int KW, int S>
+// G: the output-tile geometry.  0 (G16) = 4(z) x 4(y) x 16(x), an M-subtile is one row of 16 voxels; 1 (G8) = 4 x 8 x 8, an
+// M-subtile is two rows of 8 -- column c of the MFMA = (row c / TW, x c % TW).  Both: 256 voxels, one wave per z-plane.
+template <int KD, int KH, int KW, int S, int G = 0>
 struct FwdTile {
-  static constexpr int TD = 4, TH = 4, TW = 16;
+  static constexpr int TD = 4, TH = G ? 8 : 4, TW = G ? 8 : 16;
+  static constexpr int MR = 16 / TW;             // rows of an M-subtile
   static constexpr int TAPS = KD * KH * KW;
   static constexpr bool COMPACT = TAPS == 1;     // 1x1x1: stage exactly the voxels that are read
   static constexpr int RS = COMPACT ? 1 : S;     // x stride of a fragment read in LDS
@@ -176,8 +184,15 @@ struct FwdTile {
   static constexpr int IY = COMPACT ? TH : (TH - 1) * S + KH;
   static constexpr int IX = COMPACT ? TW : (TW - 1) * S + KW;
   static constexpr int IVOX = IZ * IY * IX;
-  static constexpr int PLANEP = pad_plane(IVOX, RS);
-  static constexpr int IN_LOADS = cdiv(IVOX, 256);
+  // LDS row stride.  G8: the two rows of an M-subtile (RS halo rows apart) must land 16 banks apart (pad_plane): a row of
+  // 10 (9) voxels is padded to 16, the stride-2 row of 17 to 24 (2 rows = 48 = 16 mod 32)
+  static constexpr int IXS = (G == 0 || COMPACT) ? IX : (RS == 1 ? 16 : 24);
+  static_assert(IX <= IXS && (G == 0 || COMPACT || (RS * IXS) % 32 == 16), "G8 row stride");
+  static constexpr int PLANEP = pad_plane(IZ * IY * IXS, RS, G);
+  // voxels staged per pass: thread t of pass i takes voxel t + i * PASS.  Padded rows: whole rows per pass, so that a
+  // thread's LDS offsets differ by a constant from pass to pass (as they do for unpadded rows)
+  static constexpr int PASS = IXS == IX ? 256 : (256 / IX) * IX;
+  static constexpr int IN_LOADS = cdiv(IVOX, PASS);
 };
 
 // SPECIAL = false: plain conv (md.in_s2d == 0, md.tap_skip == 0) -- the hot instantiation carries none of the
@@ -191,8 +206,13 @@ struct FwdTile {
 // MODE 0: plain; 1: s2d gather of the input without tap skipping (data gradient of the folded 5^3 conv); 2: the parity-folded
 // up-conv's forward (md.tap_skip == 1): live taps slot-major, (subtile, slot) MFMA loop; 3: its data gradient (s2d gather,
 // md.tap_skip == 2: the 8 live taps of the input chunk's parity, mirrored), slot-major as well.
-template <int KD, int KH, int KW, int S, int NSUB, int MODE, int REM, bool STATS = false>
-__global__ void __launch_bounds__(256)
+// waves per SIMD the register allocation is held to.  The G8 twins of the folded up-conv's forward came out one VGPR over
+// their G16 twins' occupancy step at 32 / 48 columns (65 + 32 and 81 + 48 registers): capped to 5 / 4 waves like the twins.
+template <int NSUB, int MODE, int REM, bool STATS, int G>
+constexpr int conv_min_waves() { return (G == 1 && MODE == 2 && !STATS && REM == 0) ? (NSUB == 2 ? 5 : NSUB == 3 ? 4 : 1) : 1; }
+
+template <int KD, int KH, int KW, int S, int NSUB, int MODE, int REM, bool STATS = false, int G = 0>
+__global__ void __launch_bounds__(256, (conv_min_waves<NSUB, MODE, REM, STATS, G>()))
 k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ scale,
             const float* __restrict__ shift, const float* __restrict__ res, float* __restrict__ y,
             CfunConv3dParams p, ConvMode md, int ntz, int nty, int ntx, int ncot, float* __restrict__ partial,
@@ -200,7 +220,7 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
   constexpr bool SPECIAL = MODE != 0, UPF = MODE == 2, UPD = MODE == 3;
   static_assert(!UPD || (KD == 3 && KH == 3 && KW == 3 && S == 1 && NSUB > 0 && REM == 0), "up-conv data-gradient tiles");
   static_assert(!UPF || (KD == 3 && KH == 3 && KW == 3 && S == 1 && NSUB > 0 && REM == 0), "up-conv forward tiles");
-  using T = FwdTile<KD, KH, KW, S>;
+  using T = FwdTile<KD, KH, KW, S, G>;
   constexpr int TAPS = T::TAPS, NT = 16 * NSUB + 4 * REM, NTP = row_stride(NT), NS1 = NSUB > 0 ? NSUB : 1;
   constexpr int W_ITEMS = TAPS * NT;  // float4 items per weight chunk: TAPS*4 rows x NT/4
   constexpr int W_LOADS = cdiv(W_ITEMS, 256);
@@ -224,9 +244,9 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
   int64_t in_off[T::IN_LOADS];  // element offset of the voxel's channel 0, or -1 when padded / unused
 #pragma unroll
   for (int i = 0; i < T::IN_LOADS; ++i) {
-    const int idx = tid + i * 256;
+    const int idx = tid + i * T::PASS;
     in_off[i] = -1;
-    if (idx < T::IVOX) {
+    if (tid < T::PASS && idx < T::IVOX) {
       const int ix = idx % T::IX, iy = (idx / T::IX) % T::IY, iz = idx / (T::IX * T::IY);
       int vz, vy, vx;
       if (T::COMPACT) { vz = (z0 + iz) * S - p.pd; vy = (y0 + iy) * S - p.ph; vx = (x0 + ix) * S - p.pw; }
@@ -239,6 +259,7 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
       }
     }
   }
+  const int xl0 = T::IXS == T::IX ? tid : (tid / T::IX) * T::IXS + tid % T::IX;      // LDS offset of the thread's first voxel
   // chunk c -> (offset into x added to in_off, first weight row, parity of the chunk)
   const int cpq = (SPECIAL && md.in_s2d) ? (md.in_cq >> 2) : 1;   // chunks per parity
   auto chunk_xoff = [&](int c) -> int64_t {
@@ -299,10 +320,12 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
     }
 #pragma unroll
     for (int i = 0; i < T::IN_LOADS; ++i) {
-      const int idx = tid + i * 256;
-      if (idx < T::IVOX) {
-        Xl[idx] = xin[i].x; Xl[T::PLANEP + idx] = xin[i].y;
-        Xl[2 * T::PLANEP + idx] = xin[i].z; Xl[3 * T::PLANEP + idx] = xin[i].w;
+      const int idx = tid + i * T::PASS;
+      if (tid < T::PASS && idx < T::IVOX) {
+        // (padded rows: PASS is a whole number of rows -> one base register, immediate offsets per pass, as for idx itself)
+        const int l = T::IXS == T::IX ? idx : xl0 + i * (T::PASS / T::IX) * T::IXS;
+        Xl[l] = xin[i].x; Xl[T::PLANEP + l] = xin[i].y;
+        Xl[2 * T::PLANEP + l] = xin[i].z; Xl[3 * T::PLANEP + l] = xin[i].w;
       }
     }
 #pragma unroll
@@ -328,10 +351,12 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
 #pragma unroll
   for (int q = 0; q < (REM > 0 ? REM : 1); ++q) accr[q] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const float* Xw = Xl + (lane >> 4) * T::PLANEP + (wv * T::RS * T::IY) * T::IX + (lane & 15) * T::RS;
+  // MFMA column lane&15 = voxel (row mrow, x mx) of the M-subtile (G16: 1 x 16, G8: 2 x 8)
+  const int mrow = (lane & 15) / T::TW, mx = (lane & 15) % T::TW;
+  const float* Xw = Xl + (lane >> 4) * T::PLANEP + (wv * T::RS * T::IY + mrow * T::RS) * T::IXS + mx * T::RS;
   const float* Ww = Wl + (lane >> 4) * NTP + (lane & 15);
-  // remainder quads: lane = voxel (row lane>>4, x = lane&15) of the wave's 4x16 plane; weights of channel lane&3
-  const float* Xr = Xl + ((wv * T::RS) * T::IY + (lane >> 4) * T::RS) * T::IX + (lane & 15) * T::RS;
+  // remainder quads: lane = voxel (row lane / TW, x = lane % TW) of the wave's TH x TW plane; weights of channel lane&3
+  const float* Xr = Xl + ((wv * T::RS) * T::IY + (lane / T::TW) * T::RS) * T::IXS + (lane % T::TW) * T::RS;
   const float* Wr = Wl + 16 * NSUB + (lane & 3);
 
   // p.Ci is the number of weight rows per tap; with in_s2d only the valid channels of each parity are visited
@@ -356,14 +381,14 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
 #pragma unroll
       for (int nn = 0; nn < NSUB; ++nn) {
         const int q = (cobase + nn * 16) / CqP;      // wave-uniform
-        const float* xq = Xw + (((q >> 2) * T::IY + ((q >> 1) & 1)) * T::IX + (q & 1));
+        const float* xq = Xw + (((q >> 2) * T::IY + ((q >> 1) & 1)) * T::IXS + (q & 1));
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float a = Ww[j * 4 * NTP + nn * 16];
-          const float* xt = xq + (((j >> 2) * T::IY + ((j >> 1) & 1)) * T::IX + (j & 1));
+          const float* xt = xq + (((j >> 2) * T::IY + ((j >> 1) & 1)) * T::IXS + (j & 1));
 #pragma unroll
           for (int m = 0; m < 4; ++m)
-            acc[m][nn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xt[m * T::RS * T::IX], acc[m][nn], 0, 0, 0);
+            acc[m][nn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xt[m * T::MR * T::RS * T::IXS], acc[m][nn], 0, 0, 0);
         }
 #ifndef CFUN_HIP_EMULATION
         __builtin_amdgcn_sched_barrier(0);      // one subtile's 40 LDS reads at a time: hoisted across subtiles they cost 200+ registers
@@ -373,16 +398,16 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
       // data gradient of the parity-folded up-conv: the chunk's 4 channels belong to output parity q of the forward conv and
       // meet only its 8 live taps, mirrored (tap 26 - t): the same (slot) loop with wave-uniform LDS offsets
       const int q = c / cpq;
-      const float* xq = Xw + (((2 - (q >> 2)) * T::IY + (2 - ((q >> 1) & 1))) * T::IX + (2 - (q & 1)));
+      const float* xq = Xw + (((2 - (q >> 2)) * T::IY + (2 - ((q >> 1) & 1))) * T::IXS + (2 - (q & 1)));
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float a[NS1];
 #pragma unroll
         for (int nn = 0; nn < NSUB; ++nn) a[nn] = Ww[j * 4 * NTP + nn * 16];
-        const float* xt = xq - (((j >> 2) * T::IY + ((j >> 1) & 1)) * T::IX + (j & 1));
+        const float* xt = xq - (((j >> 2) * T::IY + ((j >> 1) & 1)) * T::IXS + (j & 1));
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-          const float b = xt[m * T::RS * T::IX];
+          const float b = xt[m * T::MR * T::RS * T::IXS];
 #pragma unroll
           for (int nn = 0; nn < NSUB; ++nn) acc[m][nn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[nn], b, acc[m][nn], 0, 0, 0);
         }
@@ -405,7 +430,7 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
             for (int nn = 0; nn < NSUB; ++nn) a[nn] = Ww[tap * 4 * NTP + nn * 16];
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-              const float b = Xw[(dz * T::IY + (m * T::RS + dy)) * T::IX + dx];
+              const float b = Xw[(dz * T::IY + (m * T::MR * T::RS + dy)) * T::IXS + dx];
 #pragma unroll
               for (int nn = 0; nn < NSUB; ++nn)
                 acc[m][nn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[nn], b, acc[m][nn], 0, 0, 0);
@@ -414,7 +439,7 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
           if constexpr (REM > 0) {
             float xb[4];
 #pragma unroll
-            for (int cc = 0; cc < 4; ++cc) xb[cc] = Xr[cc * T::PLANEP + (dz * T::IY + dy) * T::IX + dx];
+            for (int cc = 0; cc < 4; ++cc) xb[cc] = Xr[cc * T::PLANEP + (dz * T::IY + dy) * T::IXS + dx];
 #pragma unroll
             for (int q = 0; q < REM; ++q)
 #pragma unroll
@@ -425,15 +450,14 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
     }
   }
 
-  // ---- epilogue.  16-wide subtiles: lane owns voxel (z0+wv, y0+m, x0+(lane&15)), channels nn*16 + (lane>>4)*4..+3;
-  // remainder quads: lane owns voxel (z0+wv, y0+(lane>>4), x0+(lane&15)), channels 16*NSUB + 4q..+3
-  const int oz = z0 + wv, ox = x0 + (lane & 15);
+  // ---- epilogue.  16-wide subtiles: lane owns voxel (z0+wv, y0+m*MR+mrow, x0+mx), channels nn*16 + (lane>>4)*4..+3;
+  // remainder quads: lane owns voxel (z0+wv, y0+lane/TW, x0+lane%TW), channels 16*NSUB + 4q..+3
+  const int oz = z0 + wv;
   constexpr bool stats_on = STATS;
-  const bool vox_ok = oz < p.Do && ox < p.Wo;
-  if (!stats_on && !vox_ok) return;
+  if (!stats_on && oz >= p.Do) return;
   if (stats_on) __syncthreads();      // every wave has left the main loop: its LDS tiles are dead, `smem` becomes `red`
-  auto emit = [&](int oy, int co, const f32x4& a4, float (&sa)[4], float (&sb)[4]) {
-    if (!vox_ok || oy >= p.Ho || co >= p.Co) return;
+  auto emit = [&](int oy, int ox, int co, const f32x4& a4, float (&sa)[4], float (&sb)[4]) {
+    if (oz >= p.Do || oy >= p.Ho || ox >= p.Wo || co >= p.Co) return;
     const int64_t v = (((int64_t)n * p.Do + oz) * p.Ho + oy) * p.Wo + ox;
     float4 r = make_float4(a4[0], a4[1], a4[2], a4[3]);
     if (gridDim.y > 1) {       // split-K partial: raw sums, plain layout
@@ -480,7 +504,7 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
     for (int nn = 0; nn < NSUB; ++nn) {
       float sa[4] = {0.f, 0.f, 0.f, 0.f}, sb[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int m = 0; m < 4; ++m) emit(y0 + m, cobase + nn * 16 + (lane >> 4) * 4, acc[m][nn], sa, sb);
+      for (int m = 0; m < 4; ++m) emit(y0 + m * T::MR + mrow, x0 + mx, cobase + nn * 16 + (lane >> 4) * 4, acc[m][nn], sa, sb);
       if constexpr (stats_on) {
         const int base = (nn * 16 / STAT_ROUND) * STAT_ROUND;
         quad_park_16(sa, sb, smem, ES, wv, lane, nn * 16 - base);
@@ -495,7 +519,7 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
 #pragma unroll
     for (int q = 0; q < REM; ++q) {
       float sa[4] = {0.f, 0.f, 0.f, 0.f}, sb[4] = {0.f, 0.f, 0.f, 0.f};
-      emit(y0 + (lane >> 4), cobase + 16 * NSUB + 4 * q, accr[q], sa, sb);
+      emit(y0 + lane / T::TW, x0 + lane % T::TW, cobase + 16 * NSUB + 4 * q, accr[q], sa, sb);
       if constexpr (stats_on) quad_park_wave(sa, sb, smem, ES, wv, lane, 16 * NSUB + 4 * q - RBASE);
     }
     if constexpr (stats_on) stat_round_flush(smem, ES, tid, RBASE, NT - RBASE, cobase, n, tile, p, md);
@@ -518,10 +542,10 @@ inline size_t splitk_workspace(int64_t nblk, int nchunks, const CfunConv3dParams
   return k > 1 ? (size_t)k * p.N * p.Do * p.Ho * p.Wo * p.Co * sizeof(float) : 0;
 }
 
-template <int KD, int KH, int KW, int S, int NSUB, int REM = 0>
+template <int KD, int KH, int KW, int S, int NSUB, int REM = 0, int G = 0>
 int launch_conv_mfma(const float* x, const float* wp, const float* scale, const float* shift, const float* res,
                      float* y, const CfunConv3dParams& p, const ConvMode& md, void* ws, size_t ws_bytes, hipStream_t st) {
-  using T = FwdTile<KD, KH, KW, S>;
+  using T = FwdTile<KD, KH, KW, S, G>;
   constexpr int NT = 16 * NSUB + 4 * REM, NTP = row_stride(NT);
   if (REM > 0 && (p.Co % NT) != 0) return CFUN_EINVAL;
   const int ntz = cdiv(p.Do, T::TD), nty = cdiv(p.Ho, T::TH), ntx = cdiv(p.Wo, T::TW), ncot = cdiv(p.Co, NT);
@@ -537,13 +561,17 @@ int launch_conv_mfma(const float* x, const float* wp, const float* scale, const 
   const int nchunks = md.in_s2d ? 8 * (md.in_cq >> 2) : (p.Ci >> 2);
   const int ksplit = splitk_factor(nblk, nchunks, p, ws_bytes);
   const bool stats = md.out_part != nullptr && ksplit == 1;      // (split-K: the finish pass takes the statistics)
-  auto kern = stats ? k_conv_mfma<KD, KH, KW, S, NSUB, 0, REM, true> : k_conv_mfma<KD, KH, KW, S, NSUB, 0, REM, false>;
+  auto kern = stats ? k_conv_mfma<KD, KH, KW, S, NSUB, 0, REM, true, G> : k_conv_mfma<KD, KH, KW, S, NSUB, 0, REM, false, G>;
   if constexpr (kHasSpecial) {
-    if (special && md.tap_skip != 1)
-      kern = stats ? k_conv_mfma<KD, KH, KW, S, NSUB, 1, REM, true> : k_conv_mfma<KD, KH, KW, S, NSUB, 1, REM, false>;
+    if constexpr (G == 0) {
+      if (special && md.tap_skip != 1)
+        kern = stats ? k_conv_mfma<KD, KH, KW, S, NSUB, 1, REM, true> : k_conv_mfma<KD, KH, KW, S, NSUB, 1, REM, false>;
+    } else {
+      if (special && md.tap_skip != 1 && !upd) return CFUN_EINVAL;      // MODE 1 has no G8 instantiation (conv3d.hip: mfma_geom)
+    }
     if constexpr (NSUB > 0 && REM == 0) {
-      if (md.tap_skip == 1) kern = stats ? k_conv_mfma<KD, KH, KW, S, NSUB, 2, 0, true> : k_conv_mfma<KD, KH, KW, S, NSUB, 2, 0, false>;
-      if (upd) kern = k_conv_mfma<KD, KH, KW, S, NSUB, 3, 0, false>;      // (a data gradient: no statistics epilogue)
+      if (md.tap_skip == 1) kern = stats ? k_conv_mfma<KD, KH, KW, S, NSUB, 2, 0, true, G> : k_conv_mfma<KD, KH, KW, S, NSUB, 2, 0, false, G>;
+      if (upd) kern = k_conv_mfma<KD, KH, KW, S, NSUB, 3, 0, false, G>;      // (a data gradient: no statistics epilogue)
     } else {
       if (md.tap_skip == 1) return CFUN_EINVAL;
     }
@@ -570,17 +598,17 @@ inline int tile_channels(int code) { return 16 * (code & 7) + 4 * (code >> 3); }
 
 // statistics slots per sample that launch_conv_mfma fills for (p, tile code nsub) given ws_bytes of split-K workspace:
 // > 0 by the conv's tiles (slot-minor layout), < 0 by the split-K finish (-(blocks), k_channel_finalize's layout)
-inline int fwd_stat_slots(int nsub, const CfunConv3dParams& p, const ConvMode& md, size_t ws_bytes) {
+inline int fwd_stat_slots(int nsub, int geom, const CfunConv3dParams& p, const ConvMode& md, size_t ws_bytes) {
   const int nt = tile_channels(nsub);
-  const int tiles = cdiv(p.Do, 4) * cdiv(p.Ho, 4) * cdiv(p.Wo, 16);
+  const int tiles = cdiv(p.Do, 4) * cdiv(p.Ho, geom ? 8 : 4) * cdiv(p.Wo, geom ? 8 : 16);
   const int64_t nblk = (int64_t)p.N * tiles * cdiv(p.Co, nt);
   const int nchunks = md.in_s2d ? 8 * (md.in_cq >> 2) : (p.Ci >> 2);
   return splitk_factor(nblk, nchunks, p, ws_bytes) > 1 ? -cfun_splitk_stat_slots(&p) : tiles * (p.d2s ? 8 : 1);
 }
 
-template <int KD, int KH, int KW, int S>
+template <int KD, int KH, int KW, int S, int G = 0>
 size_t fwd_workspace(int nsub, const CfunConv3dParams& p, const ConvMode& md) {
-  using T = FwdTile<KD, KH, KW, S>;
+  using T = FwdTile<KD, KH, KW, S, G>;
   const int nt = tile_channels(nsub);
   const int64_t nblk = (int64_t)p.N * cdiv(p.Do, T::TD) * cdiv(p.Ho, T::TH) * cdiv(p.Wo, T::TW) * cdiv(p.Co, nt);
   const int nchunks = md.in_s2d ? 8 * (md.in_cq >> 2) : (p.Ci >> 2);
@@ -596,26 +624,27 @@ constexpr bool has_rem_tiles() {
 template <int KD, int KH, int KW, int S>
 constexpr int max_nsub() { return KD * KH * KW > 27 ? 1 : 5; }   // 5x5x5: LDS / accumulator budget allows 16 channels
 
-template <int KD, int KH, int KW, int S>
+template <int KD, int KH, int KW, int S, int G = 0>
 int dispatch_nsub(int nsub, const float* x, const float* wp, const float* scale, const float* shift, const float* res,
                   float* y, const CfunConv3dParams& p, const ConvMode& flip, void* ws, size_t wsb, hipStream_t st) {
   // nsub >= 8 encodes a tile with remainder quads: nsub = NSUB + 8*REM  (tiles 20 = (1,1), 40 = (2,2), 8 = (0,2))
   if constexpr (has_rem_tiles<KD, KH, KW, S>()) {
-    if (nsub == 1 + 8 * 1) return launch_conv_mfma<KD, KH, KW, S, 1, 1>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
-    if (nsub == 2 + 8 * 2) return launch_conv_mfma<KD, KH, KW, S, 2, 2>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
-    if (nsub == 0 + 8 * 2) return launch_conv_mfma<KD, KH, KW, S, 0, 2>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
+    if (nsub == 1 + 8 * 1) return launch_conv_mfma<KD, KH, KW, S, 1, 1, G>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
+    if constexpr (G == 0)      // (pick_tile never chooses the 40-channel remainder tile: no G8 copy of it)
+      if (nsub == 2 + 8 * 2) return launch_conv_mfma<KD, KH, KW, S, 2, 2>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
+    if (nsub == 0 + 8 * 2) return launch_conv_mfma<KD, KH, KW, S, 0, 2, G>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
   }
   if (nsub >= 8 || nsub < 1) return CFUN_EINVAL;
   if constexpr (max_nsub<KD, KH, KW, S>() == 1) {
     if (nsub != 1) return CFUN_EINVAL;
-    return launch_conv_mfma<KD, KH, KW, S, 1>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
+    return launch_conv_mfma<KD, KH, KW, S, 1, 0, G>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
   } else {
     switch (nsub) {
-      case 1: return launch_conv_mfma<KD, KH, KW, S, 1>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
-      case 2: return launch_conv_mfma<KD, KH, KW, S, 2>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
-      case 3: return launch_conv_mfma<KD, KH, KW, S, 3>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
-      case 4: return launch_conv_mfma<KD, KH, KW, S, 4>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
-      default: return launch_conv_mfma<KD, KH, KW, S, 5>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
+      case 1: return launch_conv_mfma<KD, KH, KW, S, 1, 0, G>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
+      case 2: return launch_conv_mfma<KD, KH, KW, S, 2, 0, G>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
+      case 3: return launch_conv_mfma<KD, KH, KW, S, 3, 0, G>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
+      case 4: return launch_conv_mfma<KD, KH, KW, S, 4, 0, G>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
+      default: return launch_conv_mfma<KD, KH, KW, S, 5, 0, G>(x, wp, scale, shift, res, y, p, flip, ws, wsb, st);
     }
   }
 }
@@ -1227,6 +1256,31 @@ int dispatch_wgrad(const float* x, const float* g, float* partial, const CfunCon
                              const cfun_mfma::WgPlan& w, hipStream_t st) {                                          \
     return cfun_mfma::dispatch_wgrad<KD, KH, KW, S>(x, g, partial, p, w, st);                                       \
   }
+
+// the 4 x 8 x 8 output tile (G8) of the shapes the deep U-Net levels run: forward entry points only
+#define CFUN_MFMA_DECL_G8(NAME)                                                                                     \
+  int cfun_mfma_fwd_g8_##NAME(int nsub, const float* x, const float* wp, const float* scale, const float* shift,    \
+                              const float* res, float* y, const CfunConv3dParams& p,                                \
+                              const cfun_mfma::ConvMode& flip, void* ws, size_t wsb, hipStream_t st);               \
+  size_t cfun_mfma_fwd_ws_g8_##NAME(int nsub, const CfunConv3dParams& p, const cfun_mfma::ConvMode& md);
+
+#define CFUN_MFMA_DEFINE_G8(NAME, KD, KH, KW, S)                                                                    \
+  int cfun_mfma_fwd_g8_##NAME(int nsub, const float* x, const float* wp, const float* scale, const float* shift,    \
+                              const float* res, float* y, const CfunConv3dParams& p,                                \
+                              const cfun_mfma::ConvMode& flip, void* ws, size_t wsb, hipStream_t st) {              \
+    return cfun_mfma::dispatch_nsub<KD, KH, KW, S, 1>(nsub, x, wp, scale, shift, res, y, p, flip, ws, wsb, st);     \
+  }                                                                                                                 \
+  size_t cfun_mfma_fwd_ws_g8_##NAME(int nsub, const CfunConv3dParams& p, const cfun_mfma::ConvMode& md) {           \
+    return cfun_mfma::fwd_workspace<KD, KH, KW, S, 1>(nsub, p, md);                                                 \
+  }
+
+CFUN_MFMA_DECL_G8(k333s1)
+CFUN_MFMA_DECL_G8(k333s2)
+CFUN_MFMA_DECL_G8(k222s1)
+
+// conv3d.hip: the output-tile geometry (0 = G16, 1 = G8) the forward / data-gradient kernels run conv p with, given that a
+// G8 instantiation exists for it (1; 2: one that only an override may pick) -- the one rule both kernel families share
+int cfun_tile_geom(const CfunConv3dParams* p, int g8_exists);
 
 CFUN_MFMA_DECL(k333s1)
 CFUN_MFMA_DECL(k333s2)

@@ -1,0 +1,4 @@
+// the 4 x 8 x 8 output tile (G8) of the k222s1 forward / data-gradient kernels (see conv3d_mfma.h)
+#include "conv3d_mfma.h"
+
+CFUN_MFMA_DEFINE_G8(k222s1, 2, 2, 2, 1)

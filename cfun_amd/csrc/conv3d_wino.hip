@@ -11,10 +11,14 @@
 // tests/kernel_cases.py against the fp64 oracle next to the direct kernel).
 //
 //   block  = 256 threads (4 waves) -> 4(z) x 4(y) x 16(x) output voxels x (16*NSUB) output channels (same tile,
-//            raster and XCD remap as k_conv_mfma)
-//   wave w = z-plane w; MFMA columns = 2 rows x 8 x-pairs, 2 row groups; accumulators [2 row groups][4 points][NSUB]
-//   LDS    = V [4 ch][6 z][6 y][8 pairs] x float4 (the 4 points) + U [9 (dz,dy)][4 ch][16*NSUB] x float4: a fragment
-//            read is one ds_read_b128 per (dz,dy) for all 4 points (8 consecutive lanes = 128 contiguous bytes)
+//            raster and XCD remap as k_conv_mfma), or 4 x 8 x 8 (Geom<1>, "G8": the 24^3 and 6^3 levels, where 16-wide
+//            tiles are 3/4 resp. 3/8 full along x)
+//   wave w = z-plane w; MFMA columns = 2 rows x 8 x-pairs (G8: 4 rows x 4 pairs), 2 row groups; accumulators
+//            [2 row groups][4 points][NSUB]
+//   LDS    = V [4 ch][6 z][6 y][8 pairs] (G8: [6 z][10 y][4 pairs]) x float4 (the 4 points) + U [9 (dz,dy)][4 ch][16*NSUB]
+//            x float4: a fragment read is one ds_read_b128 per (dz,dy) for all 4 points; the 16 columns of a k are 256
+//            contiguous bytes in either geometry (rows follow each other without padding), so the four 16-lane groups of
+//            the read meet the banks exactly as before
 #include <stdlib.h>
 
 #include <utility>
@@ -30,8 +34,21 @@ __device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&&
 
 using cfun_mfma::cdiv;
 
-constexpr int TD = 4, TH = 4, TW = 16, IZ = 6, IY = 6, NPAIR = 8;
-constexpr int VPLANE4 = IZ * IY * NPAIR;      // float4 (= the 4 points of one x-pair) per channel of the halo tile
+// The output-tile geometry G: 0 (G16) = 4(z) x 4(y) x 16(x), 1 (G8) = 4 x 8 x 8 (conv3d.hip: cfun_tile_geom).  The 16 MFMA
+// columns of a wave are COLR rows x NPAIR x-pairs of its z-plane: 2 x 8 (G16) or 4 x 4 (G8); consecutive rows are consecutive
+// in LDS, so a fragment read covers the same 16 contiguous float4 in both.
+constexpr int TD = 4, IZ = 6;
+template <int G>
+struct Geom {
+  static constexpr int TH = G ? 8 : 4, TW = G ? 8 : 16, IY = TH + 2;
+  static constexpr int NPAIR = TW / 2;              // output pairs per row (stored per halo row)
+  static constexpr int SPAIR = NPAIR + 1;           // column pairs staged per halo row (the last one only feeds its neighbour)
+  static constexpr int COLR = 16 / NPAIR;           // rows (1-D) / 2-row y tiles (2-D) among a wave's 16 MFMA columns
+  static constexpr int ROWS_PW = 64 / SPAIR;        // whole halo rows a wave stages per pass: 7 x 9 (G16) / 12 x 5 (G8) lanes
+  static constexpr int XLANES = ROWS_PW * SPAIR;
+  static constexpr int VPLANE4 = IZ * IY * NPAIR;   // float4 (= the 4 points of one x-pair) per channel of the halo tile
+  static_assert(4 * ROWS_PW * 2 >= IZ * IY, "two staging passes cover the halo rows");
+};
 
 // u[r9][ci][co][point] from wp[tap = r9*3 + dx][ci][co]  (flip: the data gradient reads tap 26 - t)
 __global__ void __launch_bounds__(256)
@@ -83,18 +100,20 @@ k_wino2_weights(const float* __restrict__ wp, float4* __restrict__ u, int Ci, in
 // accumulators are [4 py][4 px][NSUB].
 // SB (TWOD only): one LDS buffer and two barriers per chunk like the 1-D loop, and registers capped for two waves per
 // SIMD at NSUB = 2 (128 + 128): the second resident workgroup hides the staging instead of the second buffer.
-template <int NSUB, bool S2D, bool TWOD, bool STATS = false, bool SB = false>
+template <int NSUB, bool S2D, bool TWOD, bool STATS = false, bool SB = false, int G = 0>
 __global__ void __launch_bounds__(256, (TWOD && SB) ? (NSUB == 1 ? 3 : 2) : 1)
 k_conv_wino(const float* __restrict__ x, const float4* __restrict__ u, const float* __restrict__ scale,
             const float* __restrict__ shift, const float* __restrict__ res, float* __restrict__ y, CfunConv3dParams p,
             int ntz, int nty, int ntx, int ncot, float* __restrict__ partial, int chunks_per_split, int s2d_cq,
             cfun_mfma::ConvMode md) {
+  using GM = Geom<G>;
+  constexpr int TH = GM::TH, TW = GM::TW, IY = GM::IY, NPAIR = GM::NPAIR, VPLANE4 = GM::VPLANE4;
   constexpr int NT = 16 * NSUB;
   constexpr int UROWS = TWOD ? 12 : 9;        // (dz,py) or (dz,dy) groups of 4 channel rows
   constexpr int W_ITEMS = UROWS * 4 * NT;     // float4 (= 4 x-points of one output channel) items per chunk
   constexpr int W_LOADS = cdiv(W_ITEMS, 256);
   CFUN_DYN_LDS(float4, smem);
-  float4* Vl = smem;                          // [4 ch][36 rows][8 pairs] x 4 points
+  float4* Vl = smem;                          // [4 ch][IZ * IY rows][NPAIR pairs] x 4 points
   float4* Ul = smem + 4 * VPLANE4;            // [9 (dz,dy)][4 ch][NT] x 4 points
 
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -110,20 +129,20 @@ k_conv_wino(const float* __restrict__ x, const float4* __restrict__ u, const flo
   // ---- staging descriptors.  X item = (halo row r = (z, y), column pair jj of 9): the two voxels x = 2jj, 2jj+1 for TWO
   // consecutive channel chunks (each 16-byte piece; both come out of the same 64-byte sector, so issued back to back
   // the second merges with the first's miss instead of fetching the sector from L2 again one chunk later -- the tile's
-  // 104 KB footprint does not survive in the L1 between chunks).  A wave owns 7 whole rows per pass (lane = 9*row + jj,
-  // lane 63 idle), so the two voxels an x-pair needs from the next column pair are one lane away (__shfl).  Loads are
+  // 104 KB footprint does not survive in the L1 between chunks).  A wave owns ROWS_PW whole rows per pass (G16: lane = 9*row + jj,
+  // lane 63 idle; G8: lane = 5*row + jj, 12 rows, lanes 60..63 idle), so the two voxels an x-pair needs from the next column pair are one lane away (__shfl).  Loads are
   // unconditional (out-of-volume voxels read element 0) and the zero padding is applied in commit(): selects at load time
   // made hipcc wrap every load in a branch.
-  constexpr int X_PASSES = 2;                   // 4 waves x 7 rows x 2 passes = 56 >= 36 halo rows
-  const int xrow0 = wv * 7 + lane / 9, xjj = lane % 9;
+  constexpr int X_PASSES = 2;                   // 4 waves x 7 (12) rows x 2 passes = 56 (96) >= 36 (60) halo rows
+  const int xrow0 = wv * GM::ROWS_PW + lane / GM::SPAIR, xjj = lane % GM::SPAIR;
   const float* in_ptr[X_PASSES][2];
   unsigned in_ok = 0;
 #pragma unroll
   for (int i = 0; i < X_PASSES; ++i) {
-    const int r = i * 28 + xrow0;
+    const int r = i * 4 * GM::ROWS_PW + xrow0;
 #pragma unroll
     for (int k = 0; k < 2; ++k) in_ptr[i][k] = x;
-    if (lane < 63 && r < IZ * IY) {
+    if (lane < GM::XLANES && r < IZ * IY) {
       const int vz = z0 - p.pd + r / IY, vy = y0 - p.ph + r % IY, vx = x0 - p.pw + 2 * xjj;
       if (vz >= 0 && vz < p.Di && vy >= 0 && vy < p.Hi) {
         const int64_t row = (((int64_t)n * p.Di + vz) * p.Hi + vy) * p.Wi;
@@ -188,8 +207,8 @@ k_conv_wino(const float* __restrict__ x, const float4* __restrict__ u, const flo
       for (int k = 0; k < 2; ++k)
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc) d[2 + k][cc] = __shfl(d[k][cc], (lane + 1) & 63, 64);     // voxels 2jj+2, 2jj+3
-      const int r = i * 28 + xrow0;
-      if (lane < 63 && r < IZ * IY && xjj < NPAIR) {
+      const int r = i * 4 * GM::ROWS_PW + xrow0;
+      if (lane < GM::XLANES && r < IZ * IY && xjj < NPAIR) {
         float4* v = Vl + r * NPAIR + xjj;
 #pragma unroll
         for (int cc = 0; cc < 4; ++cc)
@@ -218,9 +237,10 @@ k_conv_wino(const float* __restrict__ x, const float4* __restrict__ u, const flo
 #pragma unroll
       for (int nn = 0; nn < NSUB; ++nn) acc[mg][pt][nn] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // fragment bases (float4 = the 4 points): B column (lane & 15) = (row (lane>>3)&1 of the row group, pair lane&7),
+  // fragment bases (float4 = the 4 points): B column (lane & 15) = (row colr of the row group / y tile colr, pair colp),
   // k = channel lane>>4;  A row (lane & 15) = output channel
-  const float4* Vw0 = Vl + (lane >> 4) * VPLANE4 + (wv * IY + (TWOD ? 2 : 1) * ((lane >> 3) & 1)) * NPAIR + (lane & 7);
+  const int colr = (lane & 15) / NPAIR, colp = lane & (NPAIR - 1);
+  const float4* Vw0 = Vl + (lane >> 4) * VPLANE4 + (wv * IY + (TWOD ? 2 : 1) * colr) * NPAIR + colp;
   const float4* Uw0 = Ul + (lane >> 4) * NT + (lane & 15);
 
   const int nchunks = p.Ci >> 2;
@@ -340,7 +360,7 @@ k_conv_wino(const float* __restrict__ x, const float4* __restrict__ u, const flo
   #pragma unroll
         for (int nn = 0; nn < NSUB; ++nn) a[nn] = Uw[r9 * 4 * NT + nn * 16];
   #pragma unroll
-        for (int mg = 0; mg < 2; ++mg) b[mg] = Vw[(dz * IY + mg * 2 + dy) * NPAIR];
+        for (int mg = 0; mg < 2; ++mg) b[mg] = Vw[(dz * IY + mg * GM::COLR + dy) * NPAIR];
       };
       frag(0);
   #ifndef CFUN_HIP_EMULATION
@@ -380,8 +400,8 @@ k_conv_wino(const float* __restrict__ x, const float4* __restrict__ u, const flo
     }
   }
 
-  // ---- output transform + epilogue: lane owns voxels (z0+wv, y0+2mg+r, x0+2j+{0,1}), channels nn*16+(lane>>4)*4..+3
-  const int oz = z0 + wv, oxe = x0 + 2 * (lane & 7);
+  // ---- output transform + epilogue: lane owns voxels (z0+wv, y0+COLR*mg+colr, x0+2*colp+{0,1}), channels nn*16+(lane>>4)*4..+3
+  const int oz = z0 + wv, oxe = x0 + 2 * colp;
   constexpr bool stats_on = STATS;      // the per-tile sums of y, y*y per channel (md.out_part): its own instantiation
   if (!stats_on && oz >= p.Do) return;
   float* red = reinterpret_cast<float*>(smem);
@@ -432,8 +452,8 @@ k_conv_wino(const float* __restrict__ x, const float4* __restrict__ u, const flo
     cfun_mfma::quad_park_16(sa, sb, red, ES, wv, lane, nn * 16 - base);
     if (end % SR == 0 || end == NT) cfun_mfma::stat_round_flush(red, ES, tid, base, end - base, cobase, n, tile, p, md);
   };
-  if constexpr (TWOD) {     // Y = A^T M A: lane owns the 2 x 2 outputs of tile (ty = (lane>>3)&1, j = lane&7)
-    const int oy = y0 + 2 * ((lane >> 3) & 1);
+  if constexpr (TWOD) {     // Y = A^T M A: lane owns the 2 x 2 outputs of tile (ty = colr, j = colp)
+    const int oy = y0 + 2 * colr;
 #pragma unroll
     for (int nn = 0; nn < NSUB; ++nn) {
       float sa[4] = {0.f, 0.f, 0.f, 0.f}, sb[4] = {0.f, 0.f, 0.f, 0.f};
@@ -462,7 +482,7 @@ k_conv_wino(const float* __restrict__ x, const float4* __restrict__ u, const flo
       for (int j = 0; j < 4; ++j) { sa[nn][j] = 0.f; sb[nn][j] = 0.f; }
 #pragma unroll
     for (int mg = 0; mg < 2; ++mg) {
-      const int oy = y0 + mg * 2 + ((lane >> 3) & 1);
+      const int oy = y0 + mg * GM::COLR + colr;
 #pragma unroll
       for (int nn = 0; nn < NSUB; ++nn)
         emit(oy, oxe, cobase + nn * 16 + (lane >> 4) * 4, (acc[mg][0][nn] + acc[mg][1][nn]) + acc[mg][2][nn], sa[nn], sb[nn]);
@@ -513,20 +533,20 @@ int wino_2d(const CfunConv3dParams& p) {
     const char* e = getenv("CFUN_WINO_2D");
     knob = e ? atoi(e) : -1;
   }
-  if (p.algo == CFUN_ALGO_WINO) return 0;       // tests: the 1-D kernel
-  if (p.algo == CFUN_ALGO_WINO2 || knob == 1) return 1;
+  if (CFUN_ALGO_OF(p.algo) == CFUN_ALGO_WINO) return 0;       // tests: the 1-D kernel
+  if (CFUN_ALGO_OF(p.algo) == CFUN_ALGO_WINO2 || knob == 1) return 1;
   if (knob == 0) return 0;
   // (C_out <= 16 -- the folded 5^3 conv's data gradient -- runs one co tile: 64 accumulators, three waves per SIMD either way)
   return p.Co <= 16 || (int64_t)p.N * p.Do * p.Ho * p.Wo <= ((int64_t)1 << 19);
 }
 
 struct Plan {
-  int nsub, twod, sb, ntz, nty, ntx, ncot, ksplit, cps;
+  int nsub, twod, sb, geom, ntz, nty, ntx, ncot, ksplit, cps;
   int64_t nblk;
   size_t u_bytes, part_bytes;
 };
 
-Plan make_plan(const CfunConv3dParams& p, size_t ws_for_partials) {
+Plan make_plan(const CfunConv3dParams& p, size_t ws_for_partials, bool s2d = false) {
   static const int sb_knob = env_knob("CFUN_WINO_SB");      // 0: the double-buffered one-wave-per-SIMD loop for every NSUB
   Plan w;
   w.twod = wino_2d(p);
@@ -538,7 +558,9 @@ Plan make_plan(const CfunConv3dParams& p, size_t ws_for_partials) {
   // 1.5 GB; both in ONE launch, the 16-wide workgroup next to the 32-wide one of the same voxels, measured 2.5 ms.)
   w.sb = w.twod && w.nsub <= 2 && sb_knob != 0;
   const int nt = 16 * w.nsub;
-  w.ntz = cdiv(p.Do, TD); w.nty = cdiv(p.Ho, TH); w.ntx = cdiv(p.Wo, TW); w.ncot = cdiv(p.Co, nt);
+  // (the s2d gather runs at 96^3 only: no G8 copy.  Every G8 instantiation keeps its G16 twin's registers and waves.)
+  w.geom = cfun_tile_geom(&p, s2d ? 0 : 1);
+  w.ntz = cdiv(p.Do, TD); w.nty = cdiv(p.Ho, w.geom ? 8 : 4); w.ntx = cdiv(p.Wo, w.geom ? 8 : 16); w.ncot = cdiv(p.Co, nt);
   w.nblk = (int64_t)p.N * w.ntz * w.nty * w.ntx * w.ncot;
   w.u_bytes = cfun_align_up((size_t)(w.twod ? 48 : 36) * p.Ci * p.CoP * sizeof(float), 256);
   w.ksplit = cfun_mfma::splitk_factor(w.nblk, p.Ci >> 2, p, ws_for_partials);
@@ -547,29 +569,41 @@ Plan make_plan(const CfunConv3dParams& p, size_t ws_for_partials) {
   return w;
 }
 
-template <int NSUB>
+template <int NSUB, int G>
 int launch(const float* x, const float4* u, const float* scale, const float* shift, const float* res, float* y,
            const CfunConv3dParams& p, const Plan& w, float* partial, int s2d_cq, const cfun_mfma::ConvMode& md, hipStream_t st) {
+  constexpr int VPLANE4 = Geom<G>::VPLANE4;
   const bool sb = w.twod && w.sb && NSUB <= 2;
   const size_t lds = sb ? (size_t)(8 * VPLANE4 + 48 * 16 * NSUB) * sizeof(float4)      // [V0][V1][U]
                         : (size_t)(w.twod ? 2 : 1) * (4 * VPLANE4 + (w.twod ? 48 : 36) * 16 * NSUB) * sizeof(float4);
-  auto kern = s2d_cq ? k_conv_wino<NSUB, true, false> : k_conv_wino<NSUB, false, false>;
+  // K<S2D, TWOD, STATS, SB>: the s2d gather exists for G16 only (make_plan never plans G8 for it)
+  if (G != 0 && s2d_cq) return CFUN_EINVAL;
+  auto kern = k_conv_wino<NSUB, false, false, false, false, G>;
+  if constexpr (G == 0) {
+    if (s2d_cq) kern = k_conv_wino<NSUB, true, false>;
+  }
   if constexpr (NSUB <= 3) {     // 16 accumulator sets per wave: 64 * NSUB registers
-    if (w.twod) kern = s2d_cq ? k_conv_wino<NSUB, true, true> : k_conv_wino<NSUB, false, true>;
+    if (w.twod) kern = k_conv_wino<NSUB, false, true, false, false, G>;
+    if constexpr (G == 0) {
+      if (w.twod && s2d_cq) kern = k_conv_wino<NSUB, true, true>;
+    }
   } else if (w.twod) {
     return CFUN_EINVAL;
   }
   if constexpr (NSUB <= 2) {
-    if (sb) kern = s2d_cq ? k_conv_wino<NSUB, true, true, false, true> : k_conv_wino<NSUB, false, true, false, true>;
+    if (sb) kern = k_conv_wino<NSUB, false, true, false, true, G>;
+    if constexpr (G == 0) {
+      if (sb && s2d_cq) kern = k_conv_wino<NSUB, true, true, false, true>;
+    }
   }
   if (md.out_part) {             // epilogue statistics (forward only: never with the s2d gather)
     if (s2d_cq) return CFUN_EINVAL;
-    kern = k_conv_wino<NSUB, false, false, true>;
+    kern = k_conv_wino<NSUB, false, false, true, false, G>;
     if constexpr (NSUB <= 3) {
-      if (w.twod) kern = k_conv_wino<NSUB, false, true, true>;
+      if (w.twod) kern = k_conv_wino<NSUB, false, true, true, false, G>;
     }
     if constexpr (NSUB <= 2) {
-      if (sb) kern = k_conv_wino<NSUB, false, true, true, true>;
+      if (sb) kern = k_conv_wino<NSUB, false, true, true, true, G>;
     }
   }
   if (lds > 64 * 1024) {
@@ -598,7 +632,7 @@ static int wino_knob() {
 
 // can the Winograd kernels run this conv at all (forward; the weight gradient -- conv3d_wino_wgrad.hip -- adds its own limits)
 int cfun_wino_shape_ok(const CfunConv3dParams* p) {
-  if (wino_knob() == 0 || p->algo == CFUN_ALGO_DIRECT || p->algo == CFUN_ALGO_MFMA) return 0;
+  if (wino_knob() == 0 || CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT || CFUN_ALGO_OF(p->algo) == CFUN_ALGO_MFMA) return 0;
   // depth padding 0 / 1 / 2: depth-sharded slabs arrive with their halo planes (pd = 0; their data gradient has pd = 2)
   if (p->kd != 3 || p->kh != 3 || p->kw != 3 || p->stride != 1 || p->pd < 0 || p->pd > 2 || p->ph != 1 || p->pw != 1) return 0;
   if (p->up2 || p->tap_skip || (p->res_up2 && !p->d2s) || (p->Ci & 3) || (p->Co & 3)) return 0;
@@ -612,7 +646,7 @@ int cfun_wino_shape_ok(const CfunConv3dParams* p) {
 
 int cfun_wino_supported(const CfunConv3dParams* p) {
   if (!cfun_wino_shape_ok(p)) return 0;
-  if (wino_knob() == 1 || p->algo == CFUN_ALGO_WINO || p->algo == CFUN_ALGO_WINO2) return 1;
+  if (wino_knob() == 1 || CFUN_ALGO_OF(p->algo) == CFUN_ALGO_WINO || CFUN_ALGO_OF(p->algo) == CFUN_ALGO_WINO2) return 1;
   // (the folded 5x5x5 'finetune' conv -- d2s, C_in = 8 -- has two channel chunks and is bound by its stores: no gain measured)
   return p->Co >= 32 && p->Ci >= 16 && !p->d2s;
 }
@@ -620,7 +654,7 @@ int cfun_wino_supported(const CfunConv3dParams* p) {
 // data gradient of a depth-to-space conv p (no tap skipping, no per-parity channel padding) as the Winograd conv q over
 // the gathered hi-res gradient
 int cfun_wino_s2d_dgrad_supported(const CfunConv3dParams* p, const CfunConv3dParams* q) {
-  if (wino_knob() == 0 || p->algo == CFUN_ALGO_DIRECT || p->algo == CFUN_ALGO_MFMA) return 0;
+  if (wino_knob() == 0 || CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT || CFUN_ALGO_OF(p->algo) == CFUN_ALGO_MFMA) return 0;
   if (!p->d2s || p->tap_skip || p->up2) return 0;
   const int cqp = p->Co >> 3, cq = p->d2s_cq > 0 ? p->d2s_cq : cqp;
   if (cq != cqp || (cq & 3)) return 0;
@@ -638,9 +672,12 @@ extern "C" int cfun_conv3d_wino_plan(const CfunConv3dParams* p, int32_t out[4]) 
 }
 
 size_t cfun_wino_workspace_bytes(const CfunConv3dParams* p) {
-  const Plan w = make_plan(*p, (size_t)-1);
-  return w.u_bytes + cfun_align_up(w.part_bytes, 256);
+  const Plan w = make_plan(*p, (size_t)-1), ws2d = make_plan(*p, (size_t)-1, true);      // (enough for the s2d gather of p too)
+  return w.u_bytes + cfun_align_up(w.part_bytes > ws2d.part_bytes ? w.part_bytes : ws2d.part_bytes, 256);
 }
+
+// the output-tile geometry (0 = G16, 1 = G8) of the forward launch of p
+int cfun_wino_geom(const CfunConv3dParams* p) { return make_plan(*p, (size_t)-1).geom; }
 
 // wp: packed weights [27][Ci][CoP] of the conv that is run (the data gradient passes the transposed pack and flip = 1)
 // s2d_cq > 0: x is the hi-res gradient of a depth-to-space conv with s2d_cq channels, p->Ci = 8 * s2d_cq (see k_conv_wino)
@@ -659,9 +696,9 @@ int cfun_wino_is_2d(const CfunConv3dParams* p) { return wino_2d(*p); }
 int cfun_wino_fwd(const float* x, const float* wp, int flip, int s2d_cq, const float* scale, const float* shift,
                   const float* res, float* y, const CfunConv3dParams* p, void* ws, size_t ws_bytes,
                   const cfun_mfma::ConvMode* fz, int prepared, hipStream_t st) {
-  Plan w = make_plan(*p, 0);
+  Plan w = make_plan(*p, 0, s2d_cq > 0);
   if (!ws || ws_bytes < w.u_bytes) return CFUN_EWORKSPACE;
-  w = make_plan(*p, ws_bytes - w.u_bytes);
+  w = make_plan(*p, ws_bytes - w.u_bytes, s2d_cq > 0);
   if (w.nblk > 0x7fffffffLL) return CFUN_EINVAL;
   const float4* u = prepared ? (const float4*)wp : (const float4*)ws;
   float* partial = (float*)((char*)ws + w.u_bytes);
@@ -680,14 +717,17 @@ int cfun_wino_fwd(const float* x, const float* wp, int flip, int s2d_cq, const f
   md.out_slots = w.ntz * w.nty * w.ntx * (p->d2s ? 8 : 1);
   double* finish_part = md.out_part;
   if (w.ksplit > 1) md.out_part = nullptr;     // statistics by the split-K finish instead
-  int rc;
-  switch (w.nsub) {
-    case 1: rc = launch<1>(x, u, scale, shift, res, y, *p, w, partial, s2d_cq, md, st); break;
-    case 2: rc = launch<2>(x, u, scale, shift, res, y, *p, w, partial, s2d_cq, md, st); break;
-    case 3: rc = launch<3>(x, u, scale, shift, res, y, *p, w, partial, s2d_cq, md, st); break;
-    case 4: rc = launch<4>(x, u, scale, shift, res, y, *p, w, partial, s2d_cq, md, st); break;
-    default: rc = launch<5>(x, u, scale, shift, res, y, *p, w, partial, s2d_cq, md, st); break;
-  }
+  auto run = [&](auto g_) {
+    constexpr int G = decltype(g_)::value;
+    switch (w.nsub) {
+      case 1: return launch<1, G>(x, u, scale, shift, res, y, *p, w, partial, s2d_cq, md, st);
+      case 2: return launch<2, G>(x, u, scale, shift, res, y, *p, w, partial, s2d_cq, md, st);
+      case 3: return launch<3, G>(x, u, scale, shift, res, y, *p, w, partial, s2d_cq, md, st);
+      case 4: return launch<4, G>(x, u, scale, shift, res, y, *p, w, partial, s2d_cq, md, st);
+      default: return launch<5, G>(x, u, scale, shift, res, y, *p, w, partial, s2d_cq, md, st);
+    }
+  };
+  const int rc = w.geom ? run(std::integral_constant<int, 1>{}) : run(std::integral_constant<int, 0>{});
   if (rc) return rc;
   if (w.ksplit > 1) return cfun_splitk_finish(partial, w.ksplit, scale, shift, res, y, p, finish_part, st);
   return CFUN_OK;

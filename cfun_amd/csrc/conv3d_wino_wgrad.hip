@@ -402,8 +402,8 @@ int wino_wgrad_2d(const CfunConv3dParams& p) {
     const char* e = getenv("CFUN_WINO_WGRAD_2D");
     knob = e ? atoi(e) : -1;
   }
-  if (p.algo == CFUN_ALGO_WINO) return 0;       // tests: the 1-D kernel
-  if (p.algo == CFUN_ALGO_WINO2 || knob == 1) return 1;
+  if (CFUN_ALGO_OF(p.algo) == CFUN_ALGO_WINO) return 0;       // tests: the 1-D kernel
+  if (CFUN_ALGO_OF(p.algo) == CFUN_ALGO_WINO2 || knob == 1) return 1;
   return 0;
 }
 
@@ -452,7 +452,7 @@ int cfun_wino_wgrad_supported(const CfunConv3dParams* p) {
   if (knob == 0 || !cfun_wino_shape_ok(p)) return 0;
   const int64_t lim = (int64_t)1 << 31;      // 32-bit element offsets
   if ((int64_t)p->N * p->Di * p->Hi * p->Wi * p->Ci >= lim || (int64_t)p->N * p->Do * p->Ho * p->Wo * p->Co >= lim) return 0;
-  if (knob == 1 || p->algo == CFUN_ALGO_WINO || p->algo == CFUN_ALGO_WINO2) return 1;
+  if (knob == 1 || CFUN_ALGO_OF(p->algo) == CFUN_ALGO_WINO || CFUN_ALGO_OF(p->algo) == CFUN_ALGO_WINO2) return 1;
   if (p->d2s) return 0;       // the folded 5x5x5 conv (C_in = 8): the direct kernel's packed tap pairs win (1.03 vs 1.29 ms)
   // C_in <= 8 (packed tap groups: 7 / 14 fragment rows) and 17..20 (fused plain + packed rows) stay on the direct kernels:
   // measured with tools/bench_layers.py (8->20 0.172 vs 0.191 ms, 20->20 1.17 vs 1.20; 12->20 0.251 -> 0.189, 40->40 3.41 -> 2.65)

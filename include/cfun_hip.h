@@ -45,6 +45,13 @@ typedef void* cfun_stream_t;
 #define CFUN_ALGO_MFMA 2          /* LDS-tiled implicit GEMM on v_mfma_f32_16x16x4_f32 (Ci%4==0, Co%4==0) */
 #define CFUN_ALGO_WINO 4          /* as AUTO, but every supported 3x3x3 stride-1 conv runs the F(2,3)-along-x MFMA kernel */
 #define CFUN_ALGO_WINO2 5         /* as WINO with y in the Winograd domain as well (F(2x2,3x3) per z tap) in forward / dgrad */
+/* Per-call choice of the forward / data-gradient output tile, OR-ed into `algo` (tests, A/B runs): 4(z) x 4(y) x 16(x) or
+ * 4 x 8 x 8.  No flag = the library's rule (conv3d.hip: tile_geom_rule; process-wide override CFUN_TILE_GEOM=auto|16|8).
+ * A forced 4 x 8 x 8 falls back to 4 x 4 x 16 where the kernel has no such instantiation; the query of cfun_tile.h
+ * reports what runs.  CFUN_ALGO_OF strips the flags: the value the CFUN_ALGO_* comparisons see. */
+#define CFUN_ALGO_TILE_G16 0x100
+#define CFUN_ALGO_TILE_G8 0x200
+#define CFUN_ALGO_OF(algo) ((algo) & 0xff)
 
 int cfun_version(void);
 const char* cfun_error_string(int code);

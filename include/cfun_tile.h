@@ -1,0 +1,25 @@
+/* Output-tile query of the forward / data-gradient convolution kernels (the same shared object as cfun_hip.h).
+ *
+ * A header of its own, like cfun_sample.h: the entries of cfun_hip.h are tied one to one to cfun_amd/_lib.py's EXPORTS and
+ * to the guard tier's account of them (tests/guard.py lists the host-side queries by name); this one launches nothing and
+ * is bound through _lib.TILE_SIGNATURES. */
+#ifndef CFUN_TILE_H
+#define CFUN_TILE_H
+
+#include "cfun_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The output tile {z, y, x} of the workgroups cfun_conv3d_fwd runs for p given its full workspace: {4, 4, 16} or {4, 8, 8}
+ * (CFUN_ALGO_TILE_* in p->algo, CFUN_TILE_GEOM, or the library's rule -- conv3d.hip).  The data gradient of a stride-1 conv
+ * is the forward of its mirrored parameter set and follows the same rule on ITS output grid.
+ * Returns 0, or CFUN_EINVAL if p does not run on the MFMA / Winograd kernels (CFUN_KERNEL_MFMA / _WINO). */
+int cfun_conv3d_fwd_tile(const CfunConv3dParams* p, int32_t out[3]);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

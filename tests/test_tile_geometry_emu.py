@@ -1,0 +1,29 @@
+"""CPU tier (HIP emulator) of the output-tile geometry: every case of tile_geometry_cases.py once as G16 and once as G8."""
+import pytest
+
+import tile_geometry_cases as tg
+from cfun_amd._lib import ALGO_MFMA
+
+
+@pytest.mark.parametrize("name", sorted(tg.DIRECT_CASES))
+def test_direct_conv_both_geometries(emu, name):
+    n, dhw, ci, co, kw = tg.DIRECT_CASES[name]
+    tg.check_conv_both(emu, n, dhw, ci, co, ALGO_MFMA, kw)
+
+
+@pytest.mark.parametrize("name", sorted(tg.FOLD_CASES))
+def test_folded_up_conv_both_geometries(emu, name):
+    tg.check_fold_both(emu, *tg.FOLD_CASES[name])
+
+
+@pytest.mark.parametrize("algo", sorted(tg.WINO_ALGOS))
+@pytest.mark.parametrize("name", sorted(tg.WINO_CASES))
+def test_winograd_conv_both_geometries(emu, name, algo):
+    n, dhw, ci, co, kw = tg.WINO_CASES[name]
+    tg.check_conv_both(emu, n, dhw, ci, co, tg.WINO_ALGOS[algo], kw)
+
+
+def test_auto_selection_table(emu, monkeypatch):
+    monkeypatch.delenv("CFUN_TILE_GEOM", raising=False)
+    tg.check_auto_table()
+

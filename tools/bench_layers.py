@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Per-layer timing of the conv kernels at the cfg2 shapes (U-Net b=20, 4 RoIs at 96^3; FPN/RPN at 256x256x128).
 
-    python tools/bench_layers.py [--filter l4] [--iters 5]
+    python tools/bench_layers.py [--filter l4] [--filter-re '@24|@6'] [--iters 5]
 
 Times forward, data-gradient and weight-gradient C-ABI calls separately with HIP events on the launch stream and
 prints ms + useful TFLOP/s (2*Ci*Co*taps*voxels) for each; used to A/B kernel variants inside one process."""
 import argparse
 import ctypes as C
 import os
+import re
 import sys
 
 import torch
@@ -32,11 +33,13 @@ LAYERS = [
     ("l3.0 80->80 @48", 4, (48, 48, 48), 4 * B, 4 * B, 3, 1, ""),
     ("l2.3 up2 80->40 @24->48 (unfolded)", 4, (24, 24, 24), 4 * B, 2 * B, 3, 1, "up2"),
     ("l2.3 up2 80->40 @24->48 (folded)", 4, (24, 24, 24), 4 * B, 2 * B, 3, 1, "fold3"),
+    ("c3 s2 40->80 @48->24", 4, (48, 48, 48), 2 * B, 4 * B, 3, 2, ""),
     ("nlc_c3 80->80 @24", 4, (24, 24, 24), 4 * B, 4 * B, 3, 1, "eval"),
     ("l2.0 160->160 @24", 4, (24, 24, 24), 8 * B, 8 * B, 3, 1, ""),
     ("l1.3 up2 160->80 @12->24 (folded)", 4, (12, 12, 12), 8 * B, 4 * B, 3, 1, "fold3"),
     ("nlc_c4 160->160 @12", 4, (12, 12, 12), 8 * B, 8 * B, 3, 1, ""),
     ("l1.0 320->320 @12", 4, (12, 12, 12), 16 * B, 16 * B, 3, 1, ""),
+    ("c5 s2 160->320 @12->6", 4, (12, 12, 12), 8 * B, 16 * B, 3, 2, ""),
     ("l0.3 up2 320->160 @6->12 (folded)", 4, (6, 6, 6), 16 * B, 8 * B, 3, 1, "fold3"),
     ("nlc_c5 320->320 @6", 4, (6, 6, 6), 16 * B, 16 * B, 3, 1, ""),
     ("out_upscale 5^3 8->8 @96->192 (folded)", 4, (96, 96, 96), 8, 8, 5, 1, "fold5"),
@@ -93,7 +96,8 @@ def timeit(fn, iters):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--filter", default="")
+    ap.add_argument("--filter", default="", help="substring of the row name")
+    ap.add_argument("--filter-re", default="", help="regular expression over the row name")
     ap.add_argument("--iters", type=int, default=5)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -101,7 +105,7 @@ def main():
     print("%-44s %9s %9s %9s   %s" % ("layer", "fwd ms", "dgrad ms", "wgrad ms", "useful TFLOP/s (fwd/dgrad/wgrad)"))
     tot = [0.0, 0.0, 0.0]
     for L in LAYERS:
-        if args.filter and args.filter not in L[0]:
+        if (args.filter and args.filter not in L[0]) or (args.filter_re and not re.search(args.filter_re, L[0])):
             continue
         x, wp, spec, flops = build(*L, dev)
         p = ops._params(spec, x.shape, False, False, False)

@@ -19,7 +19,7 @@ def git_blob_sha1(path):
 
 # the kernel(s) of ONE conv call (regex over rocprofv3's kernel names; several kernels' per-dispatch averages are summed):
 # the forward / data gradient of l4.0 runs k_conv_wino<NSUB = 3, S2D = false, TWOD = false, STATS = false, SB = false>
-KERNEL = os.environ.get("CFUN_PMC_KERNEL", r"k_conv_wino<3, false, false, false, false>")
+KERNEL = os.environ.get("CFUN_PMC_KERNEL", r"k_conv_wino<3, false, false, false, false(, 0)?>")
 
 
 def kernel_label(name):
