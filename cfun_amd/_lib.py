@@ -164,6 +164,13 @@ TILE_SIGNATURES = {
 }
 TILE_EXPORTS = tuple(TILE_SIGNATURES)
 
+# The scoring entries (include/cfun_eval.h): a table of their own, for the same reason; checked by tests/test_eval_*.py.
+EVAL_SIGNATURES = {
+    "cfun_seg_confusion_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "cfun_seg_confusion": (C.c_int, [_P, _P, _I, _P, _P, _I, _P, _P, _Z, _P]),
+}
+EVAL_EXPORTS = tuple(EVAL_SIGNATURES)
+
 _lib = None
 _lib_path = None
 _is_emulator = False
@@ -184,7 +191,8 @@ def load():
             "cfun_amd: %s not found -- the HIP library is required (no CPU fallback). Build it with "
             "`make -C cfun_amd/csrc -j8` or `python -c 'import __graft_entry__ as g; g.build()'`." % path)
     lib = C.CDLL(path)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()) + \
+            list(EVAL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args

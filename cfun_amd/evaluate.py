@@ -1,0 +1,236 @@
+"""Scoring a segmentation on the device: the reference's ``test()`` entry (heart_main.py:286-360; LiTS_2017/LiTS_main.py:285-367).
+
+    seg_confusion     the (K+1) x (K+1) confusion counts of a predicted class map against a label volume, one pass over the two
+                      volumes on the device (cfun_seg_confusion)
+    SegScores         per-class IoU (utils.compute_per_class_mask_iou), foreground IoU (utils.compute_mask_iou) and Dice from
+                      those exact integer counts, in float64
+    detect_original   MaskRCNN.detect for one raw volume, un-molded into the ORIGINAL image's shape (model.py:1379-1381); the
+                      class map stays a uint8 device tensor
+    run_test          the loop of heart_main.test / LiTS_main.test: load, detect, score, optionally draw and save, mean and std
+
+The reference builds two float64 one-hot arrays [H,W,D,C-1] per case, casts them to float32 and takes the diagonal of a
+[C-1,V] x [V,C-1] product; every figure it prints is a function of the (K+1)^2 integer counts computed here.  The scoring path
+synchronises once per case: SegScores' copy of those counts to the host.
+"""
+import ctypes as C
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import _lib, model, nifti, ops
+from ._lib import check, ptr, stream, workspace
+from .ops import ptr_raw
+
+MAX_CLASSES = 15          # cfun_seg_confusion: (K + 1)^2 <= 256 bins
+
+
+def seg_confusion(pred, label, num_classes):
+    """pred: dense uint8 [D,H,W] class map on the device (what the un-mold kernels write).  label: a [D,H,W] VIEW of the label
+    volume with any strides, read in place -- for the loader's [H,W,D] array pass ``label_hwd.permute(2, 0, 1)``; nothing is
+    copied.  uint8 and int32 labels are read as they are; every other dtype is converted to int32 on the device first, which
+    TRUNCATES a non-integral float label towards zero (1.5 counts as class 1) where the reference's ``label == j + 1`` would
+    match no class.  Returns the int64 [(K+1),(K+1)] device tensor ``counts[g][p]`` = voxels with label class g and predicted
+    class p; values outside [0, K) on either side -- negative labels, stray ids -- fall into the extra row / column K, so
+    ``counts.sum()`` is always D * H * W.  Raises before any launch on a shape mismatch, a ``pred`` that is not uint8 or a
+    ``num_classes`` outside 1 .. 15."""
+    k = int(num_classes)
+    if not 1 <= k <= MAX_CLASSES:
+        raise ValueError("seg_confusion: num_classes must lie in 1 .. %d, got %d" % (MAX_CLASSES, k))
+    if pred.dtype != torch.uint8:
+        raise ValueError("seg_confusion: uint8 class map expected, got %s" % (pred.dtype,))
+    if pred.dim() != 3 or tuple(pred.shape) != tuple(label.shape):
+        raise ValueError("seg_confusion: pred %s and label %s differ in shape ([D,H,W] both)" % (tuple(pred.shape), tuple(label.shape)))
+    if pred.device != label.device:
+        raise ValueError("seg_confusion: pred and label sit on different devices")
+    d, h, w = [int(v) for v in pred.shape]
+    if d * h * w >= 1 << 31:
+        raise ValueError("seg_confusion: %d voxels, 2^31 or more" % (d * h * w))
+    lib = _lib.load()
+    if label.dtype not in (torch.uint8, torch.int32):
+        label = label.to(torch.int32)
+    counts = torch.empty((k + 1, k + 1), dtype=torch.int64, device=pred.device)
+    ws = workspace(lib.cfun_seg_confusion_workspace_bytes(d, h, w, k), pred)
+    i64, i32 = C.c_int64 * 3, C.c_int32 * 3
+    check(lib.cfun_seg_confusion(ptr(pred), ptr_raw(label), 0 if label.dtype == torch.uint8 else 1, i64(*label.stride()),
+                                 i32(d, h, w), k, ptr(counts), ptr(ws), ws.numel(), stream(pred)), "seg_confusion")
+    return counts
+
+
+class SegScores:
+    """The reference's scores from the confusion counts (one ``.cpu()`` of (K+1)^2 int64 values, then float64 on the exact
+    integers).  With ``I_j = counts[j][j]``, ``A1_j`` = row j's sum (label) and ``A2_j`` = column j's sum (prediction):
+
+        per_class_iou [K-1]   I_j / (A1_j + A2_j - I_j + 1e-6), j = 1 .. K-1         utils.compute_per_class_mask_iou
+        mask_iou              the same formula on label > 0 against pred > 0          utils.compute_mask_iou
+        dice [K-1]            2 I_j / (A1_j + A2_j + 1e-6)
+
+    ``mask_iou`` counts the "other" row / column (ids >= K) as foreground, as ``> 0`` does; its precondition is that labels are
+    non-negative (a negative label is background to the reference and "other" here).  ``dice`` is this project's definition: the
+    reference publishes a Dice figure but contains no Dice function.  ``counts`` is the numpy copy of the counts."""
+
+    def __init__(self, counts):
+        c = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+        if c.ndim != 2 or c.shape[0] != c.shape[1] or c.shape[0] < 2:
+            raise ValueError("SegScores: [(K+1),(K+1)] counts expected, got %s" % (c.shape,))
+        self.counts = c.astype(np.int64)
+        k = c.shape[0] - 1
+        self.num_classes = k
+        rows, cols = self.counts.sum(axis=1), self.counts.sum(axis=0)
+        inter = np.diagonal(self.counts)[1:k].astype(np.float64)
+        a1, a2 = rows[1:k].astype(np.float64), cols[1:k].astype(np.float64)
+        self.per_class_iou = inter / (a1 + a2 - inter + 1e-6)
+        self.dice = 2.0 * inter / (a1 + a2 + 1e-6)
+        total = int(self.counts.sum())
+        g_fg, p_fg = total - int(rows[0]), total - int(cols[0])
+        both = total - int(rows[0]) - int(cols[0]) + int(self.counts[0, 0])
+        self.mask_iou = float(both) / (float(g_fg + p_fg - both) + 1e-6)
+
+
+def _is_lits(config):
+    return hasattr(config, "PAD_IMAGE_SHAPE")
+
+
+def detect_original(hot, image):
+    """``MaskRCNN.detect`` (model.py:1341-1389; LiTS_2017/model.py:1373-1417) for ONE raw volume -- [H,W,D,1] for the heart
+    configurations, [H,W,D] for the LiTS ones: ``hot.mold_inputs``, ``predict_inference``, then the un-mold into the ORIGINAL
+    image's shape, as the reference does (``CFUNHotPath.detect_images`` un-molds into the network's).  Returns ``rois``
+    (y1,x1,z1,y2,x2,z2), ``class_ids`` and ``scores`` as ``detect`` does, ``mask_device``: the class map as a uint8 [D,H,W]
+    device tensor (``.permute(1, 2, 0)`` is the reference's [H,W,D] mask), and ``empty``: True when nothing was detected --
+    ``mask_device`` is then all zeros (the reference crashes there)."""
+    lits = _is_lits(hot.config)
+    if image.ndim != (3 if lits else 4):
+        raise ValueError("detect_original: %s volume expected, got shape %s" % ("[H,W,D]" if lits else "[H,W,D,1]", tuple(image.shape)))
+    h, w, d = [int(v) for v in image.shape[:3]]
+    molded, _, windows = hot.mold_inputs([image])
+    window = tuple(float(v) for v in windows[0])
+    det, masks = hot.predict_inference(molded[0:1], window)
+    overlap = getattr(hot.config, "UNMOLD_OVERLAP_TILE", False)
+    found = det.shape[1] > 0
+    if found:
+        probs = masks[0].permute(0, 2, 3, 4, 1).contiguous()          # [N, d, h, w, C]
+        if overlap:
+            rois, class_ids, scores, cmap = model.unmold_detections_overlap_device(det[0], probs, [1, d, h, w], window)
+        else:
+            boxes, _, keep = model._unmold_boxes(det[0], [1, d, h, w], window)
+            found = keep.shape[0] > 0
+            if found:
+                rois, class_ids, scores, cmap = model.unmold_detections_device(det[0], probs, [1, d, h, w], window)
+        found = found and rois.shape[0] > 0
+    if not found:
+        return dict(rois=np.zeros((0, 6), np.int32), class_ids=np.zeros((0,), np.int32), scores=np.zeros((0,), np.float32),
+                    mask_device=torch.zeros((d, h, w), dtype=torch.uint8, device=molded.device), empty=True)
+    return dict(rois=rois, class_ids=class_ids, scores=scores, mask_device=cmap, empty=False)
+
+
+def _load_case(case, index):
+    """-> (image [H,W,D] array, label [H,W,D] array, affine, file name, shape to save at or None)"""
+    if isinstance(case[0], (str, os.PathLike)):
+        image_path, label_path = case[0], case[1]
+        lab = nifti.load(label_path)
+        return nifti.load(image_path).get_data(), lab.get_data(), lab.affine, os.path.basename(str(image_path)), tuple(lab.shape)
+    image, label, affine = case[0], case[1], case[2]
+    name = case[3] if len(case) > 3 else "case_%d.nii" % index
+    return image, label, affine, name, (tuple(case[4]) if len(case) > 4 else None)
+
+
+def _draw_box_edges(m, roi, value=10):
+    """heart_main.py:336-348 on the [H,W,D] device map: the twelve edges of one box.  Indices are clipped to dim - 1 -- the
+    reference raises an IndexError when a box touches the far face (y2 == H and so on)."""
+    lim = [int(v) - 1 for v in m.shape]
+    y1, x1, z1, y2, x2, z2 = [min(max(int(v), 0), lim[i % 3]) for i, v in enumerate(roi)]
+    for y in (y1, y2):
+        for z in (z1, z2):
+            m[y, x1:x2, z] = value
+    for x in (x1, x2):
+        for z in (z1, z2):
+            m[y1:y2, x, z] = value
+    for y in (y1, y2):
+        for x in (x1, x2):
+            m[y, x, z1:z2] = value
+
+
+def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None):
+    """The loop of ``heart_main.test`` (and of ``LiTS_main.test`` when ``hot.config`` is a LiTS configuration).
+
+    ``cases``: each either ``(image_path, label_path)`` -- NIfTI files read with cfun_amd.nifti -- or ``(image, label, affine)``
+    arrays [H,W,D] (optionally followed by a file name and, for LiTS, the shape to save at); ``limit``: only the first so many.
+    Per case: ``detect_original``, ``seg_confusion`` of the device map against the label read in place, ``SegScores``.  Returns a
+    dict: ``per_class_ious`` [n, K-1], ``mean`` and ``std`` over the cases (axis 0), ``total_mean``, ``mask_ious`` [n], ``dice``
+    [n, K-1], ``detect_time`` (seconds, summed, as the reference measures it around detect), ``results`` (detect_original's
+    dicts) and ``saved`` (paths).
+
+    ``save_dir``: the map is written as [H,W,D] int32 with the label's affine under the reference's name rule
+    ``str(per_class_iou.mean()) + "_" + basename``; with ``draw_bbox`` the twelve edges of ``rois[0]`` are set to 10 first
+    (indices clipped to dim - 1: the reference raises an IndexError when a box touches the far face).
+
+    LiTS configurations follow LiTS_main.test: ``rois`` are clipped as at LiTS_main.py:319-323, ``draw_bbox`` fills every box with
+    100, the saved map gets an order-0 resize to the NIfTI's own shape and is stored uint8, and with a detector-only stage
+    ('beginning') the mask is zeros and the mask scores are skipped (the file name then starts with "detector": the fork's
+    box-IoU figure is not computed here)."""
+    cfg = hot.config
+    lits = _is_lits(cfg)
+    k = int(cfg.NUM_CLASSES)
+    detector_only = lits and bool(getattr(hot, "detector_phase_only", False))
+    dev = next(hot.parameters()).device
+    ious, mask_ious, dices, results, saved = [], [], [], [], []
+    detect_time = 0.0
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+    for index, case in enumerate(list(cases)[:limit]):
+        image, label, affine, name, save_shape = _load_case(case, index)
+        image_t = torch.as_tensor(image)
+        if lits:
+            image_t = image_t.to(torch.float32)
+        elif image_t.dim() == 3:
+            image_t = image_t[..., None]                              # np.expand_dims(image, -1), heart_main.py:304
+        start = time.time()
+        res = detect_original(hot, image_t)
+        detect_time += time.time() - start
+        results.append(res)
+        pred = res["mask_device"]
+        if detector_only:
+            pred = torch.zeros_like(pred)
+            res["mask_device"] = pred
+        rois = np.asarray(res["rois"])
+        h, w, d = [int(v) for v in image_t.shape[:3]]
+        if lits:
+            rois = rois.clip(min=0)
+            for axis, dim in ((3, h), (4, w), (5, d)):
+                rois[:, axis] = rois[:, axis].clip(max=dim - 1)
+            rois = res["rois"] = rois.astype(np.int32)
+        prefix = "detector"
+        if not detector_only:
+            label_t = torch.as_tensor(label).to(dev)                  # keeps the array's own strides: nothing is re-laid out
+            s = SegScores(seg_confusion(pred, label_t.permute(2, 0, 1), k))
+            ious.append(s.per_class_iou)
+            mask_ious.append(s.mask_iou)
+            dices.append(s.dice)
+            prefix = str(s.per_class_iou.mean())
+        if save_dir is None:
+            continue
+        m = pred.permute(1, 2, 0)
+        if draw_bbox and rois.shape[0]:
+            m = m.clone()
+            if lits:
+                for y1, x1, z1, y2, x2, z2 in rois.tolist():
+                    m[y1:y2, x1:x2, z1:z2] = 100
+            else:
+                _draw_box_edges(m, rois[0])
+        if lits:
+            if save_shape is not None and tuple(save_shape) != tuple(m.shape):
+                m = torch.round(ops.resize3d(m.to(torch.float32), save_shape, order=0))
+            out = m.to(torch.uint8).cpu().numpy()
+        else:
+            out = m.to(torch.int32).cpu().numpy()
+        path = os.path.join(save_dir, prefix + "_" + name)
+        nifti.save(nifti.Nifti1Image(out, affine), path)
+        saved.append(path)
+    nfg = k - 1
+    per = np.array(ious, dtype=np.float64).reshape(len(ious), nfg)
+    return dict(per_class_ious=per, mean=per.mean(axis=0) if len(ious) else np.full(nfg, np.nan),
+                std=per.std(axis=0) if len(ious) else np.full(nfg, np.nan),
+                total_mean=float(per.mean()) if len(ious) else float("nan"), mask_ious=np.array(mask_ious, dtype=np.float64),
+                dice=np.array(dices, dtype=np.float64).reshape(len(dices), nfg), detect_time=detect_time, results=results,
+                saved=saved)
