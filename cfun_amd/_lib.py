@@ -171,6 +171,15 @@ EVAL_SIGNATURES = {
 }
 EVAL_EXPORTS = tuple(EVAL_SIGNATURES)
 
+# The connected-component entries (include/cfun_cc.h): a table of their own, for the same reason; checked by tests/test_cc_*.py.
+CC_CLASS, CC_FOREGROUND = 0, 1
+CC_SIGNATURES = {
+    "cfun_cc_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "cfun_cc_label": (C.c_int, [_P, _P, _I, _I, _P, _P, _Z, _P]),
+    "cfun_cc_filter": (C.c_int, [_P, _P, _P, _I, _I, _I, _L, _P, _P, _P, _Z, _P]),
+}
+CC_EXPORTS = tuple(CC_SIGNATURES)
+
 _lib = None
 _lib_path = None
 _is_emulator = False
@@ -192,7 +201,7 @@ def load():
             "`make -C cfun_amd/csrc -j8` or `python -c 'import __graft_entry__ as g; g.build()'`." % path)
     lib = C.CDLL(path)
     for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()) + \
-            list(EVAL_SIGNATURES.items()):
+            list(EVAL_SIGNATURES.items()) + list(CC_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -92,13 +92,26 @@ def _is_lits(config):
     return hasattr(config, "PAD_IMAGE_SHAPE")
 
 
-def detect_original(hot, image):
+def _postprocess(res, postprocess, num_classes):
+    """Replace ``mask_device`` by its cleaned map; zeros in, zeros out (an empty detection passes through the same kernels)."""
+    raw = res["mask_device"]
+    res["mask_device"], res["component_stats"] = postprocess(raw, num_classes)
+    res["mask_device_raw"] = raw
+    return res
+
+
+def detect_original(hot, image, postprocess=None):
     """``MaskRCNN.detect`` (model.py:1341-1389; LiTS_2017/model.py:1373-1417) for ONE raw volume -- [H,W,D,1] for the heart
     configurations, [H,W,D] for the LiTS ones: ``hot.mold_inputs``, ``predict_inference``, then the un-mold into the ORIGINAL
     image's shape, as the reference does (``CFUNHotPath.detect_images`` un-molds into the network's).  Returns ``rois``
     (y1,x1,z1,y2,x2,z2), ``class_ids`` and ``scores`` as ``detect`` does, ``mask_device``: the class map as a uint8 [D,H,W]
     device tensor (``.permute(1, 2, 0)`` is the reference's [H,W,D] mask), and ``empty``: True when nothing was detected --
-    ``mask_device`` is then all zeros (the reference crashes there)."""
+    ``mask_device`` is then all zeros (the reference crashes there).
+
+    ``postprocess``: a ``components.Postprocess``, or None (the default: exactly the above).  With one, ``mask_device`` is the
+    map cleaned by ``components.clean_components`` -- still on the device, nothing synchronised -- and the dict gains
+    ``component_stats`` (the int64 [K,3] device tensor) and ``mask_device_raw`` (the map as un-molded).  The reference has no
+    such step."""
     lits = _is_lits(hot.config)
     if image.ndim != (3 if lits else 4):
         raise ValueError("detect_original: %s volume expected, got shape %s" % ("[H,W,D]" if lits else "[H,W,D,1]", tuple(image.shape)))
@@ -119,9 +132,13 @@ def detect_original(hot, image):
                 rois, class_ids, scores, cmap = model.unmold_detections_device(det[0], probs, [1, d, h, w], window)
         found = found and rois.shape[0] > 0
     if not found:
-        return dict(rois=np.zeros((0, 6), np.int32), class_ids=np.zeros((0,), np.int32), scores=np.zeros((0,), np.float32),
-                    mask_device=torch.zeros((d, h, w), dtype=torch.uint8, device=molded.device), empty=True)
-    return dict(rois=rois, class_ids=class_ids, scores=scores, mask_device=cmap, empty=False)
+        res = dict(rois=np.zeros((0, 6), np.int32), class_ids=np.zeros((0,), np.int32), scores=np.zeros((0,), np.float32),
+                   mask_device=torch.zeros((d, h, w), dtype=torch.uint8, device=molded.device), empty=True)
+    else:
+        res = dict(rois=rois, class_ids=class_ids, scores=scores, mask_device=cmap, empty=False)
+    if postprocess is not None:
+        _postprocess(res, postprocess, int(hot.config.NUM_CLASSES))
+    return res
 
 
 def _load_case(case, index):
@@ -151,7 +168,7 @@ def _draw_box_edges(m, roi, value=10):
             m[y, x, z1:z2] = value
 
 
-def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None):
+def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess=None):
     """The loop of ``heart_main.test`` (and of ``LiTS_main.test`` when ``hot.config`` is a LiTS configuration).
 
     ``cases``: each either ``(image_path, label_path)`` -- NIfTI files read with cfun_amd.nifti -- or ``(image, label, affine)``
@@ -168,7 +185,12 @@ def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None):
     LiTS configurations follow LiTS_main.test: ``rois`` are clipped as at LiTS_main.py:319-323, ``draw_bbox`` fills every box with
     100, the saved map gets an order-0 resize to the NIfTI's own shape and is stored uint8, and with a detector-only stage
     ('beginning') the mask is zeros and the mask scores are skipped (the file name then starts with "detector": the fork's
-    box-IoU figure is not computed here)."""
+    box-IoU figure is not computed here).
+
+    ``postprocess``: a ``components.Postprocess`` handed to ``detect_original``, or None (the default: exactly the above).  With
+    one, the cleaned map is what is scored, drawn into and saved; each result dict carries ``component_stats`` and
+    ``mask_device_raw``.  The step adds no synchronisation -- still one per case -- and the statistics stay on the device
+    until the caller reads them."""
     cfg = hot.config
     lits = _is_lits(cfg)
     k = int(cfg.NUM_CLASSES)
@@ -186,13 +208,16 @@ def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None):
         elif image_t.dim() == 3:
             image_t = image_t[..., None]                              # np.expand_dims(image, -1), heart_main.py:304
         start = time.time()
-        res = detect_original(hot, image_t)
+        res = detect_original(hot, image_t, postprocess)
         detect_time += time.time() - start
         results.append(res)
         pred = res["mask_device"]
         if detector_only:
             pred = torch.zeros_like(pred)
             res["mask_device"] = pred
+            if postprocess is not None:                               # zeros in, zeros out: the statistics of an empty map
+                res["mask_device_raw"] = pred
+                res["component_stats"] = torch.zeros_like(res["component_stats"])
         rois = np.asarray(res["rois"])
         h, w, d = [int(v) for v in image_t.shape[:3]]
         if lits:
