@@ -405,6 +405,30 @@ def check_maxpool(device, seed=3):
     # gradients routed to tied zeros may pick a different zero; compare where the input is positive
     m = (x > 0)
     assert_close(xd.grad.cpu() * m, xr.grad * m, "dx", 1e-7)
+    # ... and with NO tie mask: the kernel promises torch's rule (the first maximum in (d, h, w) scan order wins, a NaN wins
+    # over everything), so the saved index and dx are torch's, element for element -- on the ReLU input above, a constant
+    # input (every window a full tie), a sparser ReLU input and one with NaNs (one in a window, two in a window)
+    from cfun_amd import _lib
+    lib = _lib.load()
+    xn = randn(gen, 2, 4, 6, 8, 16)
+    xn[0, 1, 2, 3, 0] = float("nan")
+    xn[1, 0, 0, 0, 1] = xn[1, 1, 1, 0, 1] = float("nan")
+    for what, xi in (("relu", x), ("constant", torch.full_like(x, 0.75)), ("sparse", F.relu(randn(gen, 2, 4, 6, 8, 16) - 1.0)), ("nan", xn)):
+        xr = xi.clone().requires_grad_(True)
+        yr, flat = F.max_pool3d(xr.permute(0, 4, 1, 2, 3), 2, 2, return_indices=True)
+        yr.backward(gy.permute(0, 4, 1, 2, 3))
+        zz, rr = flat // (6 * 8), flat % (6 * 8)
+        k_ref = ((zz % 2) * 4 + ((rr // 8) % 2) * 2 + (rr % 8) % 2).permute(0, 2, 3, 4, 1).to(torch.uint8)
+        xd = xi.clone().to(device).requires_grad_(True)
+        y = ops.maxpool2(xd)
+        y.backward(gy.to(device))
+        yk, yt = y.detach().cpu(), yr.detach().permute(0, 2, 3, 4, 1)
+        assert torch.equal(torch.isnan(yk), torch.isnan(yt)) and torch.equal(torch.nan_to_num(yk), torch.nan_to_num(yt)), what + ": y"
+        assert torch.equal(xd.grad.cpu(), xr.grad), what + ": dx differs from torch with no tie mask"
+        yk2 = torch.empty_like(y)
+        idx = torch.empty(y.shape, dtype=torch.uint8, device=device)
+        assert lib.cfun_maxpool2_fwd(ops.ptr(xd.detach()), ops.ptr(yk2), ops.ptr(idx), 2, 2, 3, 4, 16, ops.stream(yk2)) == 0
+        assert torch.equal(idx.cpu(), k_ref), what + ": the saved index is not torch's choice"
 
 
 # ------------------------------------------------------------------------------------------ RoIAlign / NMS
