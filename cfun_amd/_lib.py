@@ -161,6 +161,7 @@ SAMPLE_EXPORTS = tuple(SAMPLE_SIGNATURES)
 # The output-tile query (include/cfun_tile.h): a host-side query in a table of its own, for the same reason.
 TILE_SIGNATURES = {
     "cfun_conv3d_fwd_tile": (C.c_int, [_PP, C.POINTER(C.c_int32)]),
+    "cfun_conv3d_wgrad_tile": (C.c_int, [_PP, C.POINTER(C.c_int32)]),
 }
 TILE_EXPORTS = tuple(TILE_SIGNATURES)
 

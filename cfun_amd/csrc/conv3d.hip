@@ -34,6 +34,7 @@ int cfun_stats_finalize(const double* part, float* stats, int N, int slots, int 
 int cfun_wino_wgrad_supported(const CfunConv3dParams*);
 size_t cfun_wino_wgrad_workspace_bytes(const CfunConv3dParams*);
 int cfun_wino_wgrad(const float*, const float*, float*, const CfunConv3dParams*, int*, hipStream_t);
+int cfun_wino_wgrad_geom(const CfunConv3dParams*);
 // conv3d_wgrad_c1.hip
 int cfun_wgrad_c1_supported(const CfunConv3dParams*);
 size_t cfun_wgrad_c1_ws(const CfunConv3dParams*);
@@ -56,19 +57,26 @@ struct Shape {
   int max_nsub;
   FwdFn fwd8;        // the 4 x 8 x 8 output tile (G8) of the forward / data-gradient kernel, or null
   FwdWsFn fwd_ws8;
+  PlanFn plan8;      // the TD x 8 x 8 voxel tile (G8) of the weight-gradient kernels, or null
+  WgFn wgrad8;
 };
 
-#define SHAPE(NAME, KD, KH, KW, S, MAXN) \
-  { KD, KH, KW, S, cfun_mfma_fwd_##NAME, cfun_mfma_fwd_ws_##NAME, cfun_mfma_wgrad_plan_##NAME, cfun_mfma_wgrad_##NAME, MAXN, \
-    nullptr, nullptr }
-#define SHAPE_G8(NAME, KD, KH, KW, S, MAXN) \
-  { KD, KH, KW, S, cfun_mfma_fwd_##NAME, cfun_mfma_fwd_ws_##NAME, cfun_mfma_wgrad_plan_##NAME, cfun_mfma_wgrad_##NAME, MAXN, \
-    cfun_mfma_fwd_g8_##NAME, cfun_mfma_fwd_ws_g8_##NAME }
-// G8 where the deep U-Net levels (24^3, 6^3) run: 3x3x3 stride 1 / 2 and the folded stride-2 data gradient (2x2x2)
+#define SHAPE_BASE(NAME, KD, KH, KW, S, MAXN) \
+  KD, KH, KW, S, cfun_mfma_fwd_##NAME, cfun_mfma_fwd_ws_##NAME, cfun_mfma_wgrad_plan_##NAME, cfun_mfma_wgrad_##NAME, MAXN
+#define FWD_G8(NAME) cfun_mfma_fwd_g8_##NAME, cfun_mfma_fwd_ws_g8_##NAME
+#define WGRAD_G8(NAME) cfun_mfma_wgrad_plan_g8_##NAME, cfun_mfma_wgrad_g8_##NAME
+#define NO_G8 nullptr, nullptr
+// G8 where the deep U-Net levels (24^3, 6^3) run: 3x3x3 stride 1 / 2 (both directions), the folded stride-2 data gradient
+// (2x2x2, forward kernel only) and the 1x1x1 weight gradient
 const Shape kShapes[] = {
-    SHAPE_G8(k333s1, 3, 3, 3, 1, 5), SHAPE_G8(k333s2, 3, 3, 3, 2, 5), SHAPE(k111s1, 1, 1, 1, 1, 5),
-    SHAPE(k111s2, 1, 1, 1, 2, 5), SHAPE(k133s1, 1, 3, 3, 1, 5), SHAPE(k311s1, 3, 1, 1, 1, 5),
-    SHAPE(k555s1, 5, 5, 5, 1, 1), SHAPE_G8(k222s1, 2, 2, 2, 1, 5),
+    {SHAPE_BASE(k333s1, 3, 3, 3, 1, 5), FWD_G8(k333s1), WGRAD_G8(k333s1)},
+    {SHAPE_BASE(k333s2, 3, 3, 3, 2, 5), FWD_G8(k333s2), WGRAD_G8(k333s2)},
+    {SHAPE_BASE(k111s1, 1, 1, 1, 1, 5), NO_G8, WGRAD_G8(k111s1)},
+    {SHAPE_BASE(k111s2, 1, 1, 1, 2, 5), NO_G8, NO_G8},
+    {SHAPE_BASE(k133s1, 1, 3, 3, 1, 5), NO_G8, NO_G8},
+    {SHAPE_BASE(k311s1, 3, 1, 1, 1, 5), NO_G8, NO_G8},
+    {SHAPE_BASE(k555s1, 5, 5, 5, 1, 1), NO_G8, NO_G8},
+    {SHAPE_BASE(k222s1, 2, 2, 2, 1, 5), FWD_G8(k222s1), NO_G8},
 };
 
 const Shape* find_shape(int kd, int kh, int kw, int s) {
@@ -714,6 +722,32 @@ static bool wgrad_mfma_fits(const CfunConv3dParams* p) {
   return (int64_t)p->N * p->Di * p->Hi * p->Wi * p->Ci < lim && go < lim;
 }
 
+// ---- voxel-tile geometry of the weight-gradient kernels (k_wgrad_mfma / k_wgrad_fused; k_wgrad_wino: conv3d_wino_wgrad.hip):
+// G16 = TD x 4 x 16 or G8 = TD x 8 x 8 by the forward's rule and overrides (cfun_tile_geom) on the grid the weight gradient
+// tiles -- p->Do/Ho/Wo, the low-resolution grid of a folded / depth-to-space conv.  TD is the same for both, so z cancels
+// as it does in the forward.  The plan, the workspace size and the launch all go through wgrad_geom.
+//
+// G8 twins that keep fewer waves resident than their G16 instantiation (profiles/wgrad_tile_kernel_regs.txt; none uses scratch):
+// the rule leaves them on G16, an override still runs them.  Both are the input-prologue (IN) instantiations -- the plan and
+// the workspace query do not know of the prologue, so the tile code decides:
+//   folded up-conv (TSKIP) with 80-column tiles, IN: 214 + 48 registers, 2 -> 1 waves (l0.3 of the step, 320 -> 160 @ 6^3)
+//   C_in <= 4 (PACK 4) with 64-column tiles, IN: 129 -> 137 VGPRs, 3 -> 2 waves (no conv of the supported configurations)
+// (Follow-up: a call WITHOUT the prologue keeps both waves on G8 -- l0.3 measured 0.387 -> 0.231 ms that way -- but the geometry
+// cannot follow the prologue at launch alone: cfun_conv3d_bwd_weight_workspace_bytes sizes the partials from the same plan and
+// has no fusion argument, so the query's signature would have to change with it.)
+static bool wgrad_g8_loses_wave(const CfunConv3dParams* p, const Shape* s, int nsub) {
+  if (s->kd != 3 || s->s != 1) return false;
+  return (p->d2s && p->tap_skip && nsub == 5) || (p->Ci <= 4 && nsub == 4);
+}
+
+// No no-gain list: every launch the rule switches measured faster (tools/bench_layers.py, CFUN_TILE_GEOM=16 | auto | 16 | auto in
+// one call, wgrad ms; profiles/wgrad_tile_layers.log) -- l2.3 folded 0.454 / 0.451 -> 0.350 / 0.350, c3 stride 2 0.192 / 0.192 ->
+// 0.170 / 0.170, c5 stride 2 0.129 / 0.128 -> 0.084 / 0.085, the 1x1x1 convs at 24^3 160 -> 80 0.054 / 0.053 -> 0.045 / 0.045 and
+// 160 -> 8 0.025 / 0.025 -> 0.022 / 0.022 (the Winograd launches: conv3d_wino_wgrad.hip).
+static int wgrad_geom(const CfunConv3dParams* p, const Shape* s) {
+  return cfun_tile_geom(p, !s->wgrad8 ? 0 : wgrad_g8_loses_wave(p, s, wgrad_nsub(p, s)) ? 2 : 1);
+}
+
 size_t cfun_conv3d_bwd_weight_workspace_bytes(const CfunConv3dParams* p) {
   if (!valid_params(p)) return 0;
   if (CFUN_ALGO_OF(p->algo) != CFUN_ALGO_DIRECT && cfun_wgrad_c1_supported(p)) return cfun_align_up(cfun_wgrad_c1_ws(p), 256);
@@ -721,7 +755,7 @@ size_t cfun_conv3d_bwd_weight_workspace_bytes(const CfunConv3dParams* p) {
   if (s && cfun_wino_wgrad_supported(p)) return cfun_align_up(cfun_wino_wgrad_workspace_bytes(p), 256);
   if (s) {
     cfun_mfma::WgPlan w;
-    s->plan(*p, wgrad_nsub(p, s), &w);
+    (wgrad_geom(p, s) ? s->plan8 : s->plan)(*p, wgrad_nsub(p, s), &w);
     return cfun_align_up((size_t)w.nchunks * w.kslots * p->kd * p->kh * p->kw * p->Ci * p->CoP * sizeof(float), 256);
   }
   return cfun_align_up(cfun_direct_wgrad_ws(p), 256);
@@ -753,18 +787,29 @@ static int bwd_weight_any(const float* x, const float* g, CfunWgradDst dst, cons
       return cfun_wgrad_finish((const float*)ws, dst, p, nparts, cfun_st(stream));
     }
     cfun_mfma::WgPlan w;
-    s->plan(*p, wgrad_nsub(p, s), &w);
+    const int geom = wgrad_geom(p, s);
+    (geom ? s->plan8 : s->plan)(*p, wgrad_nsub(p, s), &w);
     if (pro) {
       if (f->in_act != CFUN_ACT_NONE && (f->in_act != CFUN_ACT_LRELU || f->in_slope < 0.f || f->in_slope > 1.f)) return CFUN_EINVAL;
       w.in_stats = f->in_stats; w.in_act = CFUN_ACT_LRELU; w.in_slope = f->in_act == CFUN_ACT_LRELU ? f->in_slope : 1.f;
     }
     if (w.ntiles == 0) return cfun_wgrad_zero(dst, p, cfun_st(stream));
-    const int rc = s->wgrad(x, g, (float*)ws, *p, w, cfun_st(stream));
+    const int rc = (geom ? s->wgrad8 : s->wgrad)(x, g, (float*)ws, *p, w, cfun_st(stream));
     if (rc) return rc;
     return cfun_wgrad_finish((const float*)ws, dst, p, w.nchunks * w.kslots, cfun_st(stream));
   }
   if (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_MFMA) return CFUN_EINVAL;
   return cfun_conv_bwd_weight_direct(x, g, dst, p, ws, ws_bytes, cfun_st(stream));
+}
+
+int cfun_conv3d_wgrad_tile(const CfunConv3dParams* p, int32_t out[3]) {
+  if (!out || !valid_params(p)) return CFUN_EINVAL;
+  if (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT || cfun_wgrad_c1_supported(p) || !wgrad_mfma_fits(p)) return CFUN_EINVAL;
+  const Shape* s = mfma_shape(p);
+  if (!s) return CFUN_EINVAL;
+  const int g = cfun_wino_wgrad_supported(p) ? cfun_wino_wgrad_geom(p) : wgrad_geom(p, s);
+  out[0] = p->stride == 1 ? 2 : 1; out[1] = g ? 8 : 4; out[2] = g ? 8 : 16;
+  return CFUN_OK;
 }
 
 int cfun_conv3d_bwd_weight(const float* x, const float* g, float* dwp, const CfunConv3dParams* p, void* ws,

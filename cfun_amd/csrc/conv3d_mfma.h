@@ -14,8 +14,8 @@
 //     The next chunk's global loads are issued before the MFMA block of the current one (register prefetch).
 //
 //   weight-gradient kernel (k_wgrad_mfma):
-//     block  = 2(z) x 4(y) x 16(x) voxels per step, one 16-channel ci subtile x (16*NSUB) co, a range of
-//              spatial tiles; taps are split over the 4 waves (or the voxel groups, when taps < 4)
+//     block  = 2(z) x 4(y) x 16(x) voxels per step (or 2 x 8 x 8: WgTile's G8), one 16-channel ci subtile x (16*NSUB) co,
+//              a range of spatial tiles; taps are split over the 4 waves (or the voxel groups, when taps < 4)
 //     A = X^T (rows = ci, k = 4 consecutive voxels), B = G (k = voxels, cols = co)  =>  D[ci][co] per tap,
 //     accumulated in registers over all tiles of the block, written as a partial; a second kernel sums the
 //     partials (deterministic, no atomics).
@@ -656,9 +656,14 @@ struct WgIn {          // input prologue of the weight-gradient kernels (kernel 
   float slope;
 };
 
-template <int KD, int KH, int KW, int S>
+// G: the voxel-tile geometry, as FwdTile's.  0 (G16) = TD x 4 x 16, 1 (G8) = TD x 8 x 8 -- the voxels are the K dimension of
+// the MFMA here, so every padded voxel of a level that 16-wide tiles fill badly (24, 6) is a wasted k-step.  A k-step stays
+// 4 consecutive x of one row; TVOX, the accumulators and the partial layout do not depend on G, and the halo tile shrinks
+// (4*10*10 = 400 instead of 4*6*18 = 432 voxels; stride 2: 3*17*17 = 867 instead of 3*9*33 = 891).
+template <int KD, int KH, int KW, int S, int G = 0>
 struct WgTile {
-  static constexpr int TD = (S == 1) ? 2 : 1, TH = 4, TW = 16;   // stride 2: smaller tile, the halo tile is 4x larger
+  static constexpr int TD = (S == 1) ? 2 : 1, TH = G ? 8 : 4, TW = G ? 8 : 16;   // stride 2: smaller tile, the halo tile is 4x larger
+  static constexpr int XQ = TW / 4;          // 4-voxel groups (k-steps) per tile row
   static constexpr int TVOX = TD * TH * TW;  // 128 (64 for stride 2)
   static constexpr int TAPS = KD * KH * KW;
   static constexpr bool COMPACT = TAPS == 1;
@@ -683,12 +688,12 @@ struct WgTile {
 // IN: the input prologue (WgIn) -- x is staged as in_act((x - mean) * rstd).  The (mean, rstd) rows of the committed
 // tile's sample sit in a small LDS table behind the tiles (refilled when the sample changes, by the prefetch that runs
 // between two commits), so the plain instantiation keeps its registers and the prologue costs two LDS reads per item.
-template <int KD, int KH, int KW, int S, int NSUB, bool TSKIP, int PACK, bool IN>
+template <int KD, int KH, int KW, int S, int NSUB, bool TSKIP, int PACK, bool IN, int G>
 __device__ __forceinline__ void
 wgrad_body(float* smem, const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ partial,
            const CfunConv3dParams& p, int ntz, int nty, int ntx, int cot, int cis, int chunk, int tiles_per_chunk,
            int ntiles, const WgIn& fin) {
-  using T = WgTile<KD, KH, KW, S>;
+  using T = WgTile<KD, KH, KW, S, G>;
   constexpr int TAPS = T::TAPS, NT = 16 * NSUB, GS = pad_row16(NT);
   constexpr int NLIVE = TSKIP ? 8 : TAPS;                         // taps this block accumulates
   constexpr int R = 16 / PACK;                                    // channels per packed tap
@@ -849,7 +854,7 @@ wgrad_body(float* smem, const float* __restrict__ x, const float* __restrict__ g
 #pragma unroll 4
     for (int it = 0; it < T::TVOX / 4 / KSPLIT; ++it) {   // constant trip count: MFMA loops only unroll evenly
       const int grp = it * KSPLIT + kslot;
-      const int xq = grp & 3, ly = (grp >> 2) & 3, lz = grp >> 4;
+      const int xq = grp % T::XQ, ly = (grp / T::XQ) % T::TH, lz = grp / (T::XQ * T::TH);
       float b[NSUB], a[TPW];
 #pragma unroll
       for (int nn = 0; nn < NSUB; ++nn) b[nn] = Gw[(grp * 4) * GS + nn * 16];
@@ -898,7 +903,7 @@ wgrad_body(float* smem, const float* __restrict__ x, const float* __restrict__ g
 // Packing the remainder subtile of C_in = 20 / 40 beside plain subtiles was measured and dropped: the dispatcher
 // deals workgroups round-robin over the CUs (tools/probe_dispatch.py), the light packed workgroups finish early
 // and the kernel time stays that of the plain ones; rebalancing by tile count lost to the per-tile staging cost.
-template <int KD, int KH, int KW, int S, int NSUB, bool TSKIP, int PACK, bool IN = false>
+template <int KD, int KH, int KW, int S, int NSUB, bool TSKIP, int PACK, bool IN = false, int G = 0>
 __global__ void __launch_bounds__(256)
 k_wgrad_mfma(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ partial,
              CfunConv3dParams p, int ntz, int nty, int ntx, int ncisub, int ncot, int tiles_per_chunk, int ntiles, WgIn fin) {
@@ -907,8 +912,8 @@ k_wgrad_mfma(const float* __restrict__ x, const float* __restrict__ g, float* __
   const int cot = lid % ncot; lid /= ncot;
   const int cis = lid % ncisub;
   const int chunk = lid / ncisub;
-  wgrad_body<KD, KH, KW, S, NSUB, TSKIP, PACK, IN>(smem, x, g, partial, p, ntz, nty, ntx, cot, cis, chunk,
-                                                   tiles_per_chunk, ntiles, fin);
+  wgrad_body<KD, KH, KW, S, NSUB, TSKIP, PACK, IN, G>(smem, x, g, partial, p, ntz, nty, ntx, cot, cis, chunk,
+                                                      tiles_per_chunk, ntiles, fin);
 }
 
 // ---- C_in = 16*NPL + R with R = 16/PACK <= 8 remainder channels and 27 taps (the level-1 U-Net convs: C_in = 20 ->
@@ -928,11 +933,11 @@ inline int wgrad_fused_mode(const CfunConv3dParams& p, int nsub) {
   return 0;
 }
 
-template <int KD, int KH, int KW, int S, int NSUB, int NPL, int PACK, bool IN = false>
+template <int KD, int KH, int KW, int S, int NSUB, int NPL, int PACK, bool IN = false, int G = 0>
 __global__ void __launch_bounds__(256)
 k_wgrad_fused(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ partial, CfunConv3dParams p,
               int ntz, int nty, int ntx, int ncot, int tiles_per_chunk, int ntiles, WgIn fin) {
-  using T = WgTile<KD, KH, KW, S>;
+  using T = WgTile<KD, KH, KW, S, G>;
   constexpr int TAPS = T::TAPS, NT = 16 * NSUB, GS = pad_row16(NT);
   constexpr int R = 16 / PACK, CH = 16 * NPL + R, C4 = CH / 4;
   constexpr int XS = CH == 20 ? 24 : CH;        // floats per staged voxel; fragment reads at most 2-way conflicted
@@ -1068,7 +1073,7 @@ k_wgrad_fused(const float* __restrict__ x, const float* __restrict__ g, float* _
     if (tile + 1 < t_end) prefetch(tile + 1);
 #pragma unroll 2
     for (int grp = 0; grp < T::TVOX / 4; ++grp) {
-      const int xq = grp & 3, ly = (grp >> 2) & 3, lz = grp >> 4;
+      const int xq = grp % T::XQ, ly = (grp / T::XQ) % T::TH, lz = grp / (T::XQ * T::TH);
       float b[NSUB], a[NPL][TPW], ap[TPP];
 #pragma unroll
       for (int nn = 0; nn < NSUB; ++nn) b[nn] = Gw[(grp * 4) * GS + nn * 16];
@@ -1122,6 +1127,7 @@ k_wgrad_fused(const float* __restrict__ x, const float* __restrict__ g, float* _
 
 struct WgPlan {
   int ntz, nty, ntx, ntiles, ncisub, ncot, nchunks, tiles_per_chunk, nsub, kslots;
+  int geom;              // voxel-tile geometry the plan was made for (WgTile's G); the launch must be the same instantiation
   // input prologue (CfunConvFusion): x is read as in_act((x - mean) * rstd); set by the caller after wgrad_plan
   const float* in_stats;
   int in_act;
@@ -1129,11 +1135,12 @@ struct WgPlan {
 };
 
 
-template <int KD, int KH, int KW, int S>
+template <int KD, int KH, int KW, int S, int G = 0>
 WgPlan wgrad_plan(const CfunConv3dParams& p, int nsub) {
-  using T = WgTile<KD, KH, KW, S>;
+  using T = WgTile<KD, KH, KW, S, G>;
   WgPlan w;
   w.nsub = nsub;
+  w.geom = G;
   w.ntz = cdiv(p.Do, T::TD); w.nty = cdiv(p.Ho, T::TH); w.ntx = cdiv(p.Wo, T::TW);
   w.ntiles = p.N * w.ntz * w.nty * w.ntx;
   w.ncisub = (wgrad_fused_shape<KD, KH, KW, S>() && wgrad_fused_mode(p, nsub)) ? 1 : cdiv(p.Ci, 16);
@@ -1151,10 +1158,11 @@ WgPlan wgrad_plan(const CfunConv3dParams& p, int nsub) {
   return w;
 }
 
-template <int KD, int KH, int KW, int S, int NSUB>
+template <int KD, int KH, int KW, int S, int NSUB, int G = 0>
 int launch_wgrad_mfma(const float* x, const float* g, float* partial, const CfunConv3dParams& p, const WgPlan& w,
                       hipStream_t st) {
-  using T = WgTile<KD, KH, KW, S>;
+  using T = WgTile<KD, KH, KW, S, G>;
+  if (w.geom != G) return CFUN_EINVAL;
   constexpr int NT = 16 * NSUB, GS = pad_row16(NT);
   const size_t lds = (size_t)(T::IVOX * T::XS + T::TVOX * GS) * sizeof(float) + 8 * sizeof(float4);      // (+ stats table)
   // the kernel addresses x and g with 32-bit element offsets
@@ -1167,9 +1175,9 @@ int launch_wgrad_mfma(const float* x, const float* g, float* partial, const Cfun
       const size_t ldsf = (size_t)(T::IVOX * xs + T::TVOX * GS) * sizeof(float) + 2 * (xs / 4) * sizeof(float4);   // (+ stats table)
       const bool in = w.in_stats != nullptr || w.in_act != CFUN_ACT_NONE;
       void (*kf)(const float*, const float*, float*, CfunConv3dParams, int, int, int, int, int, int, WgIn) =
-          in ? k_wgrad_fused<KD, KH, KW, S, NSUB, 1, 4, true> : k_wgrad_fused<KD, KH, KW, S, NSUB, 1, 4, false>;
+          in ? k_wgrad_fused<KD, KH, KW, S, NSUB, 1, 4, true, G> : k_wgrad_fused<KD, KH, KW, S, NSUB, 1, 4, false, G>;
       if constexpr (S == 1) {
-        if ((mode & 15) == 2) kf = in ? k_wgrad_fused<KD, KH, KW, S, NSUB, 2, 2, true> : k_wgrad_fused<KD, KH, KW, S, NSUB, 2, 2, false>;
+        if ((mode & 15) == 2) kf = in ? k_wgrad_fused<KD, KH, KW, S, NSUB, 2, 2, true, G> : k_wgrad_fused<KD, KH, KW, S, NSUB, 2, 2, false, G>;
       }
       if (ldsf > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsf);
@@ -1182,21 +1190,21 @@ int launch_wgrad_mfma(const float* x, const float* g, float* partial, const Cfun
     }
   }
   const bool in = w.in_stats != nullptr || w.in_act != CFUN_ACT_NONE;
-  auto kern = k_wgrad_mfma<KD, KH, KW, S, NSUB, false, 1, false>;
+  auto kern = k_wgrad_mfma<KD, KH, KW, S, NSUB, false, 1, false, G>;
   auto pick = [&](auto in_c) {
     constexpr bool I = decltype(in_c)::value;
-    kern = k_wgrad_mfma<KD, KH, KW, S, NSUB, false, 1, I>;
+    kern = k_wgrad_mfma<KD, KH, KW, S, NSUB, false, 1, I, G>;
     if constexpr (KD * KH * KW == 27) {   // C_in <= 8: PACK taps per A fragment
       const int pack = w.ncisub > 1 ? 1 : p.Ci <= 4 ? 4 : p.Ci <= 8 ? 2 : 1;
       const bool ts = S == 1 && p.d2s && p.tap_skip;
       if constexpr (S == 1) {
-        if (ts) kern = pack == 4 ? k_wgrad_mfma<KD, KH, KW, S, NSUB, true, 4, I>
-                     : pack == 2 ? k_wgrad_mfma<KD, KH, KW, S, NSUB, true, 2, I>
-                                 : k_wgrad_mfma<KD, KH, KW, S, NSUB, true, 1, I>;
+        if (ts) kern = pack == 4 ? k_wgrad_mfma<KD, KH, KW, S, NSUB, true, 4, I, G>
+                     : pack == 2 ? k_wgrad_mfma<KD, KH, KW, S, NSUB, true, 2, I, G>
+                                 : k_wgrad_mfma<KD, KH, KW, S, NSUB, true, 1, I, G>;
       }
-      if (!ts) kern = pack == 4 ? k_wgrad_mfma<KD, KH, KW, S, NSUB, false, 4, I>
-                    : pack == 2 ? k_wgrad_mfma<KD, KH, KW, S, NSUB, false, 2, I>
-                                : k_wgrad_mfma<KD, KH, KW, S, NSUB, false, 1, I>;
+      if (!ts) kern = pack == 4 ? k_wgrad_mfma<KD, KH, KW, S, NSUB, false, 4, I, G>
+                    : pack == 2 ? k_wgrad_mfma<KD, KH, KW, S, NSUB, false, 2, I, G>
+                                : k_wgrad_mfma<KD, KH, KW, S, NSUB, false, 1, I, G>;
     }
   };
   if (in) pick(std::true_type{}); else pick(std::false_type{});
@@ -1211,19 +1219,19 @@ int launch_wgrad_mfma(const float* x, const float* g, float* partial, const Cfun
   return CFUN_OK;
 }
 
-template <int KD, int KH, int KW, int S>
+template <int KD, int KH, int KW, int S, int G = 0>
 int dispatch_wgrad(const float* x, const float* g, float* partial, const CfunConv3dParams& p, const WgPlan& w,
                    hipStream_t st) {
   if constexpr (max_nsub<KD, KH, KW, S>() == 1) {
     if (w.nsub != 1) return CFUN_EINVAL;
-    return launch_wgrad_mfma<KD, KH, KW, S, 1>(x, g, partial, p, w, st);
+    return launch_wgrad_mfma<KD, KH, KW, S, 1, G>(x, g, partial, p, w, st);
   } else {
     switch (w.nsub) {
-      case 1: return launch_wgrad_mfma<KD, KH, KW, S, 1>(x, g, partial, p, w, st);
-      case 2: return launch_wgrad_mfma<KD, KH, KW, S, 2>(x, g, partial, p, w, st);
-      case 3: return launch_wgrad_mfma<KD, KH, KW, S, 3>(x, g, partial, p, w, st);
-      case 4: return launch_wgrad_mfma<KD, KH, KW, S, 4>(x, g, partial, p, w, st);
-      default: return launch_wgrad_mfma<KD, KH, KW, S, 5>(x, g, partial, p, w, st);
+      case 1: return launch_wgrad_mfma<KD, KH, KW, S, 1, G>(x, g, partial, p, w, st);
+      case 2: return launch_wgrad_mfma<KD, KH, KW, S, 2, G>(x, g, partial, p, w, st);
+      case 3: return launch_wgrad_mfma<KD, KH, KW, S, 3, G>(x, g, partial, p, w, st);
+      case 4: return launch_wgrad_mfma<KD, KH, KW, S, 4, G>(x, g, partial, p, w, st);
+      default: return launch_wgrad_mfma<KD, KH, KW, S, 5, G>(x, g, partial, p, w, st);
     }
   }
 }
@@ -1277,6 +1285,25 @@ int dispatch_wgrad(const float* x, const float* g, float* partial, const CfunCon
 CFUN_MFMA_DECL_G8(k333s1)
 CFUN_MFMA_DECL_G8(k333s2)
 CFUN_MFMA_DECL_G8(k222s1)
+
+// the TD x 8 x 8 voxel tile (G8) of the weight-gradient kernels (translation units of their own: conv3d_wgrad_*_g8.hip)
+#define CFUN_WGRAD_DECL_G8(NAME)                                                                                    \
+  void cfun_mfma_wgrad_plan_g8_##NAME(const CfunConv3dParams& p, int nsub, cfun_mfma::WgPlan* w);                   \
+  int cfun_mfma_wgrad_g8_##NAME(const float* x, const float* g, float* partial, const CfunConv3dParams& p,          \
+                                const cfun_mfma::WgPlan& w, hipStream_t st);
+
+#define CFUN_WGRAD_DEFINE_G8(NAME, KD, KH, KW, S)                                                                   \
+  void cfun_mfma_wgrad_plan_g8_##NAME(const CfunConv3dParams& p, int nsub, cfun_mfma::WgPlan* w) {                  \
+    *w = cfun_mfma::wgrad_plan<KD, KH, KW, S, 1>(p, nsub);                                                          \
+  }                                                                                                                 \
+  int cfun_mfma_wgrad_g8_##NAME(const float* x, const float* g, float* partial, const CfunConv3dParams& p,          \
+                                const cfun_mfma::WgPlan& w, hipStream_t st) {                                       \
+    return cfun_mfma::dispatch_wgrad<KD, KH, KW, S, 1>(x, g, partial, p, w, st);                                    \
+  }
+
+CFUN_WGRAD_DECL_G8(k333s1)
+CFUN_WGRAD_DECL_G8(k333s2)
+CFUN_WGRAD_DECL_G8(k111s1)
 
 // conv3d.hip: the output-tile geometry (0 = G16, 1 = G8) the forward / data-gradient kernels run conv p with, given that a
 // G8 instantiation exists for it (1; 2: one that only an override may pick) -- the one rule both kernel families share

@@ -10,9 +10,11 @@ int cfun_wino_shape_ok(const CfunConv3dParams* p);      // conv3d_wino.hip
 //   dU_p[ci][co] += V_p[ci] * dM_p[co],   dM = (g_e, g_e + g_o, g_e - g_o, -g_o),   V as in the forward kernel
 // replace the 2 x 3 products of the direct sum; at the end dW = G^T dU:
 //   dw0 = dU0 + (dU1 + dU2)/2,  dw1 = (dU1 - dU2)/2,  dw2 = dU3 + (dU1 + dU2)/2.
-//   block  = 256 threads, one 16-channel ci subtile x (16*NSUB) co, a range of 2(z) x 4(y) x 16(x) voxel tiles
+//   block  = 256 threads, one 16-channel ci subtile x (16*NSUB) co, a range of 2(z) x 4(y) x 16(x) voxel tiles (G16) or
+//            2 x 8 x 8 (G8, WgGeom: the levels 16-wide tiles fill badly -- 24, 6; selection: cfun_tile_geom)
 //   wave w = Winograd point w: all 9 (dz,dy) offsets -> accumulators [9][NSUB]; MFMA k-step = 4 consecutive x-pairs
-//   LDS    = the raw halo tile [24 rows][x parity][9][16 ci] and gradient tile [8 rows][x parity][8][co]: V and dM are
+//   LDS    = the raw halo tile [24 rows][x parity][9][16 ci] and gradient tile [8 rows][x parity][8][co] (G8: [40 rows]
+//            [parity][5][16 ci] and [16 rows][parity][4][co] -- 400 instead of 432 staged voxels): V and dM are
 //            formed from two LDS reads each when the fragment is read (V_p = X[o1] + s*X[o2], dM_p = a*g_e + b*g_o with
 //            wave-uniform offsets / signs), so the tiles stay as small as the direct kernel's
 //   end    = per (dz,dy) the four waves' sums meet in LDS, G^T is applied and the 3 taps are written in the partial
@@ -26,16 +28,29 @@ constexpr int WG_XVOX = WG_XROWS * 2 * WG_XH;                  // 432 staged vox
 constexpr int WG_GVOX = 2 * 4 * 16;                            // 128 gradient voxels
 constexpr int WG_XROW = 2 * WG_XH * 16;                        // floats per halo row
 
-template <int NSUB, bool D2S>
-__global__ void __launch_bounds__(256)
+// tile geometry of k_wgrad_wino: G = 0 the constants above, G = 1 the 2 x 8 x 8 tile.  Both: 128 gradient voxels = 16 groups
+// of one output row x one quad of 4 x-pairs (G16: 8 rows x 2 quads, G8: 16 rows x 1 quad).
+template <int G>
+struct WgGeom {
+  static constexpr int TH = G ? 8 : 4, TW = G ? 8 : 16;
+  static constexpr int IY = TH + 2, XH = TW / 2 + 1;      // halo rows per z; columns per x parity
+  static constexpr int XROWS = 4 * IY, XVOX = XROWS * 2 * XH, XROW = 2 * XH * 16;
+  static constexpr int JP = TW / 2, QR = JP / 4;          // x-pairs per output row; quads of 4 pairs per row
+};
+static_assert(WgGeom<0>::IY == WG_IY && WgGeom<0>::XH == WG_XH && WgGeom<0>::XVOX == WG_XVOX && WgGeom<0>::XROW == WG_XROW, "G16");
+
+template <int NSUB, bool D2S, int G>
+__global__ void __launch_bounds__(256, (G == 1 && NSUB == 2 && !D2S) ? 3 : 1)
 k_wgrad_wino(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ partial, CfunConv3dParams p,
              int ntz, int nty, int ntx, int ncisub, int ncot, int tiles_per_chunk, int ntiles) {
+  using W = WgGeom<G>;
+  constexpr int WG_IY = W::IY, WG_XH = W::XH, WG_XVOX = W::XVOX, WG_XROW = W::XROW, JP = W::JP, QR = W::QR;      // (shadow the G16 constants)
   constexpr int NT = 16 * NSUB, GS = cfun_mfma::pad_row16(NT);
   constexpr int X_ITEMS = WG_XVOX * 4, X_LOADS = cdiv(X_ITEMS, 256);
   constexpr int G_ITEMS = WG_GVOX * (NT / 4), G_LOADS = cdiv(G_ITEMS, 256);
   CFUN_DYN_LDS(float4, smem4);
-  float* Xl = reinterpret_cast<float*>(smem4);      // [row][parity][9][16]
-  float* Gl = Xl + WG_XVOX * 16;                    // [(lrow*2 + parity)*8 + j][GS]
+  float* Xl = reinterpret_cast<float*>(smem4);      // [row][parity][XH][16]
+  float* Gl = Xl + WG_XVOX * 16;                    // [(lrow*2 + parity)*JP + j][GS]
 
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   unsigned lid = cfun_mfma::xcd_remap(blockIdx.x, gridDim.x);
@@ -59,7 +74,7 @@ k_wgrad_wino(const float* __restrict__ x, const float* __restrict__ g, float* __
     const int ty = t % nty; t /= nty;
     const int tz = t % ntz;
     const int n = t / ntz;
-    const int z0 = tz * 2, y0 = ty * 4, x0 = tx * 16;
+    const int z0 = tz * 2, y0 = ty * W::TH, x0 = tx * W::TW;
     xvalid = 0; gvalid = 0;
 #pragma unroll
     for (int i = 0; i < X_LOADS; ++i) {
@@ -76,8 +91,8 @@ k_wgrad_wino(const float* __restrict__ x, const float* __restrict__ g, float* __
     for (int i = 0; i < G_LOADS; ++i) {
       const int it = tid + i * 256;
       const int slot = it / (NT / 4), col = (it % (NT / 4)) * 4;
-      const int j = slot & 7, par = (slot >> 3) & 1, lrow = slot >> 4;
-      const int oz = z0 + (lrow >> 2), oy = y0 + (lrow & 3), ox = x0 + 2 * j + par;
+      const int j = slot % JP, par = (slot / JP) & 1, lrow = slot / (2 * JP);
+      const int oz = z0 + lrow / W::TH, oy = y0 + lrow % W::TH, ox = x0 + 2 * j + par;
       bool ok = (it < G_ITEMS) & (cobase + col < p.Co) & (oz < p.Do) & (oy < p.Ho) & (ox < p.Wo);
       unsigned off;
       if (D2S) {   // g is the hi-res gradient of y [N,2Do,2Ho,2Wo,Cq]: gather parity q, channel o
@@ -111,7 +126,7 @@ k_wgrad_wino(const float* __restrict__ x, const float* __restrict__ g, float* __
     }
   };
 
-  // point of this wave: V_p = X[o1] + s2 * X[o2] over (E[j], O[j], E[j+1], O[j+1]) = float offsets (0, 144, 16, 160);
+  // point of this wave: V_p = X[o1] + s2 * X[o2] over (E[j], O[j], E[j+1], O[j+1]) = float offsets (0, XH*16, 16, XH*16 + 16);
   // dM_p = ce * g_e + cg * g_o
   const int o1 = wv == 0 ? 0 : wv == 2 ? 16 : WG_XH * 16;
   const int o2 = wv == 2 ? WG_XH * 16 : wv == 3 ? WG_XH * 16 + 16 : 16;
@@ -132,13 +147,13 @@ k_wgrad_wino(const float* __restrict__ x, const float* __restrict__ g, float* __
     if (tile + 1 < t_end) prefetch(tile + 1);
 #pragma unroll 1
     for (int grp = 0; grp < 16; ++grp) {       // (output row lrow = (lz, ly), quad q of 4 x-pairs)
-      const int lrow = grp >> 1, q = grp & 1;
-      const int hrow = (lrow >> 2) * WG_IY + (lrow & 3);
+      const int lrow = grp / QR, q = grp % QR;
+      const int hrow = (lrow / W::TH) * WG_IY + lrow % W::TH;
       float b[NSUB], a[9];
 #pragma unroll
       for (int nn = 0; nn < NSUB; ++nn) {
-        const float* gp = Gw + ((lrow * 2) * 8 + q * 4) * GS + nn * 16;
-        b[nn] = ce * gp[0] + cg * gp[8 * GS];
+        const float* gp = Gw + ((lrow * 2) * JP + q * 4) * GS + nn * 16;
+        b[nn] = ce * gp[0] + cg * gp[JP * GS];
       }
       const float* x1 = Xa1 + hrow * WG_XROW + q * 64;
       const float* x2 = Xa2 + hrow * WG_XROW + q * 64;
@@ -365,13 +380,29 @@ k_wgrad_wino2(const float* __restrict__ x, const float* __restrict__ g, float* _
 }
 
 struct WgPlanW {
-  int nsub, ntz, nty, ntx, ntiles, ncisub, ncot, nchunks, tiles_per_chunk;
+  int nsub, ntz, nty, ntx, ntiles, ncisub, ncot, nchunks, tiles_per_chunk, geom;
 };
+
+int wino_wgrad_2d(const CfunConv3dParams& p);
+
+int wino_wgrad_nsub(const CfunConv3dParams& p) {      // fewest padded columns, widest on ties
+  return p.CoP <= 16 ? 1 : ((p.CoP + 31) / 32 * 32 < (p.CoP + 47) / 48 * 48 ? 2 : 3);
+}
+
+// The 2-D kernel has no G8 instantiation.  k_wgrad_wino<3, D2S> on G8 keeps 1 wave instead of 2 (149 + 108 registers,
+// profiles/wgrad_tile_kernel_regs.txt): only an override picks it (a depth-to-space conv reaches this kernel through
+// CFUN_ALGO_WINO alone).  <2, false> on G8 needed one VGPR more than three waves leave (97 + 72 of 168): it is held to three
+// by its launch bounds, without scratch.
+int wino_wgrad_geom(const CfunConv3dParams& p) {
+  if (wino_wgrad_2d(p)) return 0;
+  return cfun_tile_geom(&p, p.d2s && wino_wgrad_nsub(p) == 3 ? 2 : 1);
+}
 
 WgPlanW make_wg_plan(const CfunConv3dParams& p) {
   WgPlanW w;
-  w.nsub = p.CoP <= 16 ? 1 : ((p.CoP + 31) / 32 * 32 < (p.CoP + 47) / 48 * 48 ? 2 : 3);   // fewest padded columns, widest on ties
-  w.ntz = cdiv(p.Do, 2); w.nty = cdiv(p.Ho, 4); w.ntx = cdiv(p.Wo, 16);
+  w.geom = wino_wgrad_geom(p);
+  w.nsub = wino_wgrad_nsub(p);
+  w.ntz = cdiv(p.Do, 2); w.nty = cdiv(p.Ho, w.geom ? 8 : 4); w.ntx = cdiv(p.Wo, w.geom ? 8 : 16);
   w.ntiles = p.N * w.ntz * w.nty * w.ntx;
   w.ncisub = cdiv(p.Ci, 16);
   w.ncot = cdiv(p.CoP, 16 * w.nsub);
@@ -424,13 +455,13 @@ int launch_wg2(const float* x, const float* g, float* partial, const CfunConv3dP
   return CFUN_OK;
 }
 
-template <int NSUB>
+template <int NSUB, int G>
 int launch_wg(const float* x, const float* g, float* partial, const CfunConv3dParams& p, const WgPlanW& w, hipStream_t st) {
   constexpr int GS = cfun_mfma::pad_row16(16 * NSUB);
-  size_t lds = (size_t)(WG_XVOX * 16 + WG_GVOX * GS) * sizeof(float);
+  size_t lds = (size_t)(WgGeom<G>::XVOX * 16 + WG_GVOX * GS) * sizeof(float);
   const size_t scratch = (size_t)4 * 16 * 16 * NSUB * sizeof(float);
   if (lds < scratch) lds = scratch;
-  auto kern = p.d2s ? k_wgrad_wino<NSUB, true> : k_wgrad_wino<NSUB, false>;
+  auto kern = p.d2s ? k_wgrad_wino<NSUB, true, G> : k_wgrad_wino<NSUB, false, G>;
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
@@ -459,6 +490,8 @@ int cfun_wino_wgrad_supported(const CfunConv3dParams* p) {
   return !(p->Ci <= 8 || (p->Ci > 16 && p->Ci <= 20));
 }
 
+int cfun_wino_wgrad_geom(const CfunConv3dParams* p) { return wino_wgrad_geom(*p); }
+
 size_t cfun_wino_wgrad_workspace_bytes(const CfunConv3dParams* p) {
   const WgPlanW w = make_wg_plan(*p);
   return (size_t)w.nchunks * 27 * p->Ci * p->CoP * sizeof(float);
@@ -475,9 +508,16 @@ int cfun_wino_wgrad(const float* x, const float* g, float* ws, const CfunConv3dP
       default: return launch_wg2<3>(x, g, ws, *p, w, st);
     }
   }
+  if (w.geom) {
+    switch (w.nsub) {
+      case 1: return launch_wg<1, 1>(x, g, ws, *p, w, st);
+      case 2: return launch_wg<2, 1>(x, g, ws, *p, w, st);
+      default: return launch_wg<3, 1>(x, g, ws, *p, w, st);
+    }
+  }
   switch (w.nsub) {
-    case 1: return launch_wg<1>(x, g, ws, *p, w, st);
-    case 2: return launch_wg<2>(x, g, ws, *p, w, st);
-    default: return launch_wg<3>(x, g, ws, *p, w, st);
+    case 1: return launch_wg<1, 0>(x, g, ws, *p, w, st);
+    case 2: return launch_wg<2, 0>(x, g, ws, *p, w, st);
+    default: return launch_wg<3, 0>(x, g, ws, *p, w, st);
   }
 }

@@ -1,4 +1,4 @@
-/* Output-tile query of the forward / data-gradient convolution kernels (the same shared object as cfun_hip.h).
+/* Tile queries of the convolution kernels: forward / data gradient and weight gradient (the same shared object as cfun_hip.h).
  *
  * A header of its own, like cfun_sample.h: the entries of cfun_hip.h are tied one to one to cfun_amd/_lib.py's EXPORTS and
  * to the guard tier's account of them (tests/guard.py lists the host-side queries by name); this one launches nothing and
@@ -17,6 +17,12 @@ extern "C" {
  * is the forward of its mirrored parameter set and follows the same rule on ITS output grid.
  * Returns 0, or CFUN_EINVAL if p does not run on the MFMA / Winograd kernels (CFUN_KERNEL_MFMA / _WINO). */
 int cfun_conv3d_fwd_tile(const CfunConv3dParams* p, int32_t out[3]);
+
+/* The voxel tile {z, y, x} of the workgroups cfun_conv3d_bwd_weight runs for p: {2, 4, 16} or {2, 8, 8} ({1, ...} at stride 2),
+ * by the same flags, knob and rule on the grid the weight gradient tiles (p->Do/Ho/Wo; the low-resolution grid of a folded /
+ * depth-to-space conv).  {.., 4, 16} where no 8 x 8 instantiation exists (the opt-in 2-D Winograd kernel, 1x3x3, 5x5x5 ...).
+ * Returns 0, or CFUN_EINVAL if the weight gradient of p does not run on the MFMA / Winograd weight-gradient kernels. */
+int cfun_conv3d_wgrad_tile(const CfunConv3dParams* p, int32_t out[3]);
 
 #ifdef __cplusplus
 }
