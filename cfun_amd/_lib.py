@@ -181,6 +181,16 @@ CC_SIGNATURES = {
 }
 CC_EXPORTS = tuple(CC_SIGNATURES)
 
+# The surface-distance entries (include/cfun_surface.h): a table of their own, for the same reason; checked by
+# tests/test_surface_*.py.  One CfunSurfaceStats row is SURFACE_STATS_FIELDS 8-byte values: two int64 counts, then doubles.
+SURFACE_STATS_FIELDS = 11
+SURFACE_SIGNATURES = {
+    "cfun_surface_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "cfun_surface_field": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "cfun_surface_stats": (C.c_int, [_P, _P, _P, _I, _P, _D, _P, _P, _Z, _P]),
+}
+SURFACE_EXPORTS = tuple(SURFACE_SIGNATURES)
+
 _lib = None
 _lib_path = None
 _is_emulator = False
@@ -202,7 +212,7 @@ def load():
             "`make -C cfun_amd/csrc -j8` or `python -c 'import __graft_entry__ as g; g.build()'`." % path)
     lib = C.CDLL(path)
     for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()) + \
-            list(EVAL_SIGNATURES.items()) + list(CC_SIGNATURES.items()):
+            list(EVAL_SIGNATURES.items()) + list(CC_SIGNATURES.items()) + list(SURFACE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -7,6 +7,11 @@
     detect_original   MaskRCNN.detect for one raw volume, un-molded into the ORIGINAL image's shape (model.py:1379-1381); the
                       class map stays a uint8 device tensor
     run_test          the loop of heart_main.test / LiTS_main.test: load, detect, score, optionally draw and save, mean and std
+    surface_field     the surface voxels of one class and their exact squared Euclidean distance field (cfun_surface_field)
+    surface_distances per class the sums, maxima and order statistics of the surface distances between two maps, one record
+                      per class left on the device (cfun_surface_stats)
+    SurfaceScores     Hausdorff, HD95, ASSD and RMSD from those records, in float64 (the reference has no such scores: the
+                      pin is tests/surface_ref.py)
 
 The reference builds two float64 one-hot arrays [H,W,D,C-1] per case, casts them to float32 and takes the diagonal of a
 [C-1,V] x [V,C-1] product; every figure it prints is a function of the (K+1)^2 integer counts computed here.  The scoring path
@@ -24,6 +29,7 @@ from ._lib import check, ptr, stream, workspace
 from .ops import ptr_raw
 
 MAX_CLASSES = 15          # cfun_seg_confusion: (K + 1)^2 <= 256 bins
+MAX_SURFACE_DIM = 4096    # cfun_surface_*: float(k * k) exact
 
 
 def seg_confusion(pred, label, num_classes):
@@ -86,6 +92,138 @@ class SegScores:
         g_fg, p_fg = total - int(rows[0]), total - int(cols[0])
         both = total - int(rows[0]) - int(cols[0]) + int(self.counts[0, 0])
         self.mask_iou = float(both) / (float(g_fg + p_fg - both) + 1e-6)
+
+
+def _spacing2(what, spacing):
+    """(sz, sy, sx) in millimetres -> the three float32 squares the kernels take: float32(double(s) * double(s))."""
+    sp = [float(v) for v in spacing]
+    if len(sp) != 3:
+        raise ValueError("%s: spacing must be (sz, sy, sx), got %r" % (what, spacing))
+    with np.errstate(over="ignore"):
+        sq = [float(np.float32(np.float64(v) * np.float64(v))) for v in sp]
+    if not all(v > 0.0 and np.isfinite(q) and q > 0.0 for v, q in zip(sp, sq)):
+        raise ValueError("%s: every spacing must be finite and positive with a finite, positive float32 square, got %r"
+                         % (what, spacing))
+    return (C.c_float * 3)(*sq)
+
+
+def _check_surface_map(what, pred):
+    if not torch.is_tensor(pred) or pred.dtype != torch.uint8:
+        raise ValueError("%s: uint8 class map expected, got %s" % (what, getattr(pred, "dtype", type(pred))))
+    if pred.dim() != 3:
+        raise ValueError("%s: a [D,H,W] map expected, got shape %s" % (what, tuple(pred.shape)))
+    d, h, w = [int(v) for v in pred.shape]
+    if max(d, h, w) > MAX_SURFACE_DIM:
+        raise ValueError("%s: a dimension above %d in %s" % (what, MAX_SURFACE_DIM, (d, h, w)))
+    if d * h * w >= (1 << 31) - 1:
+        raise ValueError("%s: %d voxels, 2^31 - 1 or more" % (what, d * h * w))
+    return d, h, w
+
+
+def surface_field(map, cls, spacing):
+    """map: dense uint8 [D,H,W] class map on the device; ``cls`` in 1 .. 255; ``spacing`` = (sz, sy, sx) in millimetres.
+    Returns ``(surface, d2)``, both device tensors: uint8 [D,H,W], 1 on the voxels of class ``cls`` with a face neighbour
+    that is outside the volume or of another class; float32 [D,H,W], the squared distance in mm^2 from every voxel to the
+    nearest surface voxel (+inf everywhere when there is none), bit-identical to the float32 brute force of
+    include/cfun_surface.h.  Nothing synchronises.  Raises before any launch on a map that is not uint8 [D,H,W], a dimension
+    above 4096, 2^31 - 1 voxels or more, a ``cls`` outside 1 .. 255 or a spacing that is not finite and positive."""
+    dims = _check_surface_map("surface_field", map)
+    c = int(cls)
+    if not 1 <= c <= 255:
+        raise ValueError("surface_field: cls must lie in 1 .. 255, got %d" % c)
+    s2 = _spacing2("surface_field", spacing)
+    lib = _lib.load()
+    surface = torch.empty(dims, dtype=torch.uint8, device=map.device)
+    field = torch.empty(dims, dtype=torch.float32, device=map.device)
+    ws = workspace(0, map)
+    check(lib.cfun_surface_field(ptr(map), (C.c_int32 * 3)(*dims), c, s2, ptr(surface), ptr(field), ptr(ws), ws.numel(),
+                                 stream(map)), "surface_field")
+    return surface, field
+
+
+def surface_distances(pred, label, num_classes, spacing, percentile=95.0):
+    """pred: dense uint8 [D,H,W] class map on the device.  label: any [D,H,W] view of the label volume, of any integer or
+    float dtype (for the loader's [H,W,D] array pass ``label_hwd.permute(2, 0, 1)``).  The kernels take two dense uint8 maps,
+    so the label is turned into one with torch first -- a few element-wise passes over the volume, not a kernel of this
+    library: a float label is truncated towards zero as ``seg_confusion`` does, and ids outside [0, K) become K, which
+    belongs to no class on either side.  ``spacing`` = (sz, sy, sx) in millimetres; ``percentile`` in 0 .. 100.
+
+    Returns the int64 [K, 11] device tensor of CfunSurfaceStats records (include/cfun_surface.h), one per class, row 0 all
+    zeros: columns 0 and 1 are the counts, columns 2 .. 10 hold the bits of nine doubles.  ``SurfaceScores`` reads it.
+    Nothing synchronises.  Raises before any launch on a shape mismatch, a ``pred`` that is not uint8 [D,H,W], tensors on
+    different devices, a ``num_classes`` outside 1 .. 15, a dimension above 4096, 2^31 - 1 voxels or more, a spacing that is
+    not finite and positive or a ``percentile`` outside 0 .. 100."""
+    k = int(num_classes)
+    if not 1 <= k <= MAX_CLASSES:
+        raise ValueError("surface_distances: num_classes must lie in 1 .. %d, got %d" % (MAX_CLASSES, k))
+    dims = _check_surface_map("surface_distances", pred)
+    if not torch.is_tensor(label) or tuple(label.shape) != tuple(pred.shape):
+        raise ValueError("surface_distances: pred %s and label %s differ in shape ([D,H,W] both)"
+                         % (tuple(pred.shape), tuple(getattr(label, "shape", ()))))
+    if pred.device != label.device:
+        raise ValueError("surface_distances: pred and label sit on different devices")
+    q = float(percentile)
+    if not 0.0 <= q <= 100.0:
+        raise ValueError("surface_distances: percentile must lie in 0 .. 100, got %r" % (percentile,))
+    s2 = _spacing2("surface_distances", spacing)
+    if label.is_floating_point():
+        label = torch.trunc(label)
+    elif label.dtype == torch.bool:
+        label = label.to(torch.uint8)
+    label = torch.where((label >= 0) & (label < k), label, k).to(torch.uint8).contiguous()
+    lib = _lib.load()
+    stats = torch.empty((k, _lib.SURFACE_STATS_FIELDS), dtype=torch.int64, device=pred.device)
+    ws = workspace(lib.cfun_surface_workspace_bytes(*dims, k), pred)
+    check(lib.cfun_surface_stats(ptr(pred), ptr(label), (C.c_int32 * 3)(*dims), k, s2, q / 100.0, ptr(stats), ptr(ws), ws.numel(),
+                                 stream(pred)), "surface_stats")
+    return stats
+
+
+class SurfaceScores:
+    """Surface-distance scores from ``surface_distances``' records: one ``.cpu()`` of K x 11 values, then float64 on the host.
+    With A and B the surfaces of class j in the prediction and the label, d(a, B) the distance in mm from a voxel to the
+    nearest voxel of B, every array [K-1] for the classes 1 .. K-1:
+
+        hausdorff             max(max over A of d(a, B), max over B of d(b, A))
+        hd_percentile         the ``percentile`` of the concatenation {d(a, B)} u {d(b, A)}, numpy's linear rule (HD95 at 95)
+        asd_pred_to_label     mean over A of d(a, B)
+        asd_label_to_pred     mean over B of d(b, A)
+        assd                  the mean of those two directed means
+        assd_pooled           (sum over A of d(a, B) + sum over B of d(b, A)) / (|A| + |B|), the other definition in use
+        rmsd                  sqrt((sum over A of d(a, B)^2 + sum over B of d(b, A)^2) / (|A| + |B|))
+        n_pred, n_label       |A|, |B| (int64)
+
+    A class whose surface is empty on either side has ``nan`` in every score.  ``records`` is the numpy copy [K, 11]."""
+
+    def __init__(self, stats):
+        r = stats.detach().cpu().numpy() if torch.is_tensor(stats) else np.asarray(stats)
+        if r.ndim != 2 or r.shape[1] != _lib.SURFACE_STATS_FIELDS or r.shape[0] < 1 or r.dtype != np.int64:
+            raise ValueError("SurfaceScores: int64 [K, %d] records expected, got %s %s" % (_lib.SURFACE_STATS_FIELDS, r.dtype, r.shape))
+        self.records = np.ascontiguousarray(r)
+        self.num_classes = r.shape[0]
+        v = self.records[1:, 2:].copy().view(np.float64)
+        self.n_pred, self.n_label = self.records[1:, 0].copy(), self.records[1:, 1].copy()
+        sum_pl, sum_lp, sumsq_pl, sumsq_lp, max_pl, max_lp, q_lo, q_hi, frac = [v[:, i] for i in range(9)]
+        self.frac = frac
+        npred, nlab = self.n_pred.astype(np.float64), self.n_label.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ok = (self.n_pred > 0) & (self.n_label > 0)
+            nan = np.full(v.shape[0], np.nan)
+            self.hausdorff = np.where(ok, np.sqrt(np.maximum(max_pl, max_lp)), nan)
+            self.hd_percentile = np.where(ok, (1.0 - frac) * np.sqrt(q_lo) + frac * np.sqrt(q_hi), nan)
+            self.asd_pred_to_label = np.where(ok, sum_pl / npred, nan)
+            self.asd_label_to_pred = np.where(ok, sum_lp / nlab, nan)
+            self.assd = 0.5 * (self.asd_pred_to_label + self.asd_label_to_pred)
+            self.assd_pooled = np.where(ok, (sum_pl + sum_lp) / (npred + nlab), nan)
+            self.rmsd = np.where(ok, np.sqrt((sumsq_pl + sumsq_lp) / (npred + nlab)), nan)
+
+
+def affine_spacing(affine):
+    """(sz, sy, sx) of the device map [D,H,W] from the affine of the loader's [H,W,D] array: the column norms of its 3 x 3
+    part are the spacings along H, W and D."""
+    a = np.asarray(affine, dtype=np.float64)
+    sh, sw, sd = [float(np.linalg.norm(a[:3, i])) for i in range(3)]
+    return sd, sh, sw
 
 
 def _is_lits(config):
@@ -168,7 +306,7 @@ def _draw_box_edges(m, roi, value=10):
             m[y, x, z1:z2] = value
 
 
-def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess=None):
+def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess=None, surface=None):
     """The loop of ``heart_main.test`` (and of ``LiTS_main.test`` when ``hot.config`` is a LiTS configuration).
 
     ``cases``: each either ``(image_path, label_path)`` -- NIfTI files read with cfun_amd.nifti -- or ``(image, label, affine)``
@@ -190,13 +328,27 @@ def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess
     ``postprocess``: a ``components.Postprocess`` handed to ``detect_original``, or None (the default: exactly the above).  With
     one, the cleaned map is what is scored, drawn into and saved; each result dict carries ``component_stats`` and
     ``mask_device_raw``.  The step adds no synchronisation -- still one per case -- and the statistics stay on the device
-    until the caller reads them."""
+    until the caller reads them.
+
+    ``surface``: None (the default: exactly the above), True, or a percentile in 0 .. 100 (True means 95).  With one,
+    ``surface_distances`` runs on the map that is scored -- the cleaned one when ``postprocess`` is given -- against the label,
+    with the voxel spacing taken from the label's affine (``affine_spacing``).  The dict gains ``hausdorff``, ``hd95`` (the
+    chosen percentile) and ``assd``, each [n, K-1] in millimetres, and each result carries its ``SurfaceScores`` under
+    ``surface_scores``.  The records are read right after the confusion counts with nothing enqueued in between: still one
+    point of synchronisation per case.  Detector-only LiTS runs skip it, as they skip the mask scores."""
     cfg = hot.config
     lits = _is_lits(cfg)
     k = int(cfg.NUM_CLASSES)
     detector_only = lits and bool(getattr(hot, "detector_phase_only", False))
     dev = next(hot.parameters()).device
     ious, mask_ious, dices, results, saved = [], [], [], [], []
+    hds, hdqs, assds = [], [], []
+    if surface is not None and surface is not False:
+        percentile = 95.0 if surface is True else float(surface)
+        if not 0.0 <= percentile <= 100.0:
+            raise ValueError("run_test: surface must be None, True or a percentile in 0 .. 100, got %r" % (surface,))
+    else:
+        percentile = None
     detect_time = 0.0
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
@@ -228,7 +380,15 @@ def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess
         prefix = "detector"
         if not detector_only:
             label_t = torch.as_tensor(label).to(dev)                  # keeps the array's own strides: nothing is re-laid out
-            s = SegScores(seg_confusion(pred, label_t.permute(2, 0, 1), k))
+            counts = seg_confusion(pred, label_t.permute(2, 0, 1), k)
+            if percentile is not None:
+                records = surface_distances(pred, label_t.permute(2, 0, 1), k, affine_spacing(affine), percentile)
+            s = SegScores(counts)
+            if percentile is not None:                                # (nothing was enqueued since the counts were read)
+                ss = res["surface_scores"] = SurfaceScores(records)
+                hds.append(ss.hausdorff)
+                hdqs.append(ss.hd_percentile)
+                assds.append(ss.assd)
             ious.append(s.per_class_iou)
             mask_ious.append(s.mask_iou)
             dices.append(s.dice)
@@ -254,8 +414,12 @@ def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess
         saved.append(path)
     nfg = k - 1
     per = np.array(ious, dtype=np.float64).reshape(len(ious), nfg)
-    return dict(per_class_ious=per, mean=per.mean(axis=0) if len(ious) else np.full(nfg, np.nan),
-                std=per.std(axis=0) if len(ious) else np.full(nfg, np.nan),
-                total_mean=float(per.mean()) if len(ious) else float("nan"), mask_ious=np.array(mask_ious, dtype=np.float64),
-                dice=np.array(dices, dtype=np.float64).reshape(len(dices), nfg), detect_time=detect_time, results=results,
-                saved=saved)
+    summary = dict(per_class_ious=per, mean=per.mean(axis=0) if len(ious) else np.full(nfg, np.nan),
+                   std=per.std(axis=0) if len(ious) else np.full(nfg, np.nan),
+                   total_mean=float(per.mean()) if len(ious) else float("nan"), mask_ious=np.array(mask_ious, dtype=np.float64),
+                   dice=np.array(dices, dtype=np.float64).reshape(len(dices), nfg), detect_time=detect_time, results=results,
+                   saved=saved)
+    if percentile is not None:
+        for key, rows in (("hausdorff", hds), ("hd95", hdqs), ("assd", assds)):
+            summary[key] = np.array(rows, dtype=np.float64).reshape(len(rows), nfg)
+    return summary
