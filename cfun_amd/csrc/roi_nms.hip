@@ -233,7 +233,7 @@ k_nms_scan(const unsigned long long* __restrict__ mask, const int32_t* __restric
   unsigned long long cur[CH], nxt[CH];
 #pragma unroll
   for (int r = 0; r < CH; ++r) cur[r] = (r < n && lane < W64) ? mask[(int64_t)r * W64 + lane] : 0ull;
-  bool done = (max_num <= 0);
+  bool done = false;        // max_num <= 0 still keeps the top box: utils.py:146-148 appends before it tests the limit
   for (int base = 0; base < n && !done; base += CH) {
 #pragma unroll
     for (int r = 0; r < CH; ++r) {
@@ -285,7 +285,7 @@ k_nms_scan_lds(const unsigned long long* __restrict__ mask, const int32_t* __res
   const int lane = threadIdx.x;
   unsigned long long removed = 0ull;
   int cnt = 0;
-  bool done = (max_num <= 0);
+  bool done = false;        // max_num <= 0 still keeps the top box: utils.py:146-148 appends before it tests the limit
   for (int blk = 0; blk < W64 && !done; ++blk) {
     const int lim = n - blk * 64;
     const unsigned long long valid = lim >= 64 ? ~0ull : ((1ull << lim) - 1ull);
@@ -310,9 +310,9 @@ inline int next_pow2(int n) {
 }
 
 // GT mask targets (model.py:481-493): crop the uint8 label volume with int()-truncated box bounds (computed by the
-// caller in fp32, as the reference does) and nearest-resize it to the mask shape: output voxel o reads input voxel
-// floor((o + 0.5) * in / out) of the crop (the order-0 resize of utils.py:318-339).  One-hot GT channels resized
-// independently and arg-maxed give exactly this label volume.  Empty crop => zeros.
+// caller in fp32, as the reference does; applied with python slice semantics) and nearest-resize it to the mask shape:
+// output voxel o reads input voxel floor((o + 0.5) * in / out) of the crop (the order-0 resize of utils.py:318-339).
+// One-hot GT channels resized independently and arg-maxed give exactly this label volume.  Empty crop => zeros.
 __global__ void __launch_bounds__(256)
 k_mask_target_labels(const uint8_t* __restrict__ labels, const int32_t* __restrict__ bounds, uint8_t* __restrict__ out,
                      int64_t total, int D, int H, int W, int md, int mh, int mw) {
@@ -323,9 +323,10 @@ k_mask_target_labels(const uint8_t* __restrict__ labels, const int32_t* __restri
     const int z = (int)(t % md);
     const int r = (int)(t / md);
     const int32_t* b = bounds + r * 6;
-    int z1 = b[0], y1 = b[1], x1 = b[2], z2 = b[3], y2 = b[4], x2 = b[5];
-    z1 = z1 < 0 ? 0 : z1; y1 = y1 < 0 ? 0 : y1; x1 = x1 < 0 ? 0 : x1;
-    z2 = z2 > D ? D : z2; y2 = y2 > H ? H : y2; x2 = x2 > W ? W : x2;
+    int z1, y1, x1, z2, y2, x2;          // gt_masks[:, z1:z2, y1:y2, x1:x2]: negative bounds wrap, upper bounds clamp
+    py_slice(b[0], b[3], D, &z1, &z2);
+    py_slice(b[1], b[4], H, &y1, &y2);
+    py_slice(b[2], b[5], W, &x1, &x2);
     uint8_t v = 0;
     if (z2 > z1 && y2 > y1 && x2 > x1) {
       const int cd = z2 - z1, ch = y2 - y1, cw = x2 - x1;
@@ -577,7 +578,7 @@ int cfun_nms3d(const float* boxes, const float* scores, int32_t n, float thresho
   hipLaunchKernelGGL(k_nms_sort, dim3(1), dim3(1024), (size_t)np2 * 8, cfun_st(stream), boxes, scores, n, np2, order, sboxes, svol);
   hipLaunchKernelGGL(k_nms_mask, dim3((n * W64 + 255) / 256), dim3(256), 0, cfun_st(stream), sboxes, svol, n, W64, threshold, mask);
   const size_t lds = (size_t)n * W64 * sizeof(unsigned long long);
-  static int scan_knob = -1;       // CFUN_NMS_SCAN_LDS = 0: the row-by-row kernel for every n (A/B, tests)
+  static int scan_knob = -1;       // CFUN_NMS_SCAN_LDS = 0: the row-by-row kernel for every n (A/B; the head tier runs a child process with it)
   if (scan_knob < 0) { const char* e = getenv("CFUN_NMS_SCAN_LDS"); scan_knob = e ? atoi(e) : 1; }
   // The LDS-resident scan may use all of a CU's LDS.  The limit is asked of the device once and the kernel's dynamic-LDS
   // ceiling raised to it once (it used to be set on every call, the 160 KB of gfx950 were hard-coded and a raw

@@ -288,7 +288,8 @@ int cfun_edge_raw_bwd(const float* dc, const float* gscale, float* dprobs, int32
 
 /* GT mask targets of detection_target_layer (model.py:481-493, utils.py:318-339) as uint8 class labels:
  * labels [D,H,W] (class id per voxel = argmax of the one-hot GT), bounds [R,6] int32 voxel crop
- * (z1,y1,x1,z2,y2,x2) = int(shape * normalised coordinate), out [R,md,mh,mw] = nearest-resized crop. */
+ * (z1,y1,x1,z2,y2,x2) = int(shape * normalised coordinate), applied as the python slice z1:z2 (negative
+ * bounds wrap, upper bounds clamp; an empty crop gives zeros), out [R,md,mh,mw] = nearest-resized crop. */
 int cfun_mask_target_labels(const uint8_t* labels, const int32_t* bounds, uint8_t* out, int32_t R, int32_t D,
                             int32_t H, int32_t W, int32_t md, int32_t mh, int32_t mw, cfun_stream_t stream);
 
@@ -317,6 +318,7 @@ int cfun_roi_align3d_slab_bwd(const float* dout, const int32_t* bounds, float* d
 /* ------------------------------------------------------------------------------------------------
  * Greedy 3-D NMS (utils.py:122-157 + compute_iou utils.py:50-70): fp32 IoU in numpy's operation
  * order (no FMA contraction), iou > threshold suppresses, stops after max_num picks.
+ * The limit is tested after a pick, as the reference does: max_num <= 0 still keeps the top box.
  * boxes [n,6], scores [n], n <= 4096.  keep [max(n,1)] int32 (pick order), count [1] int32.
  * Ties in score are ordered higher-original-index first.
  * ---------------------------------------------------------------------------------------------- */

@@ -362,8 +362,11 @@ def check_roi_align_slabs(device, seed=33):
 
 
 def check_fc(device, seed=35):
-    """The weight-streaming FC kernels (classifier head) against torch, including the weight gradient in row chunks
-    when the rows' g + x slices exceed the kernel's LDS (wide layers)."""
+    """The weight-streaming FC kernels (classifier head) against torch fp32 through ops.fc, shift and ReLU only: four shapes
+    with K <= 200, i.e. ONE 256-wide K chunk each (one workgroup of k_fc_fwd / k_fc_bwd_weight, one row group of k_fc_finish,
+    one k block of k_fc_bwd_data), including the weight gradient in row chunks when the rows' g + x slices exceed the
+    kernel's LDS (wide layers).  Several chunks, more than 64 of them, the R / O edges, the scale epilogue, the refusals of
+    the C ABI and run-to-run identity are head_cases.check_fc_abi / check_fc_ops / check_fc_refusals, against float64."""
     from cfun_amd import _lib
     gen = _gen(seed)
     lib = _lib.load()

@@ -127,8 +127,9 @@ def hold(case, what, got, ref64, ref32, seg=None, start=0, keep=None):
     # bound 0/0: there the denominator is the whole tensor's max-abs.
     den = torch.where(mr > 1e-6 * whole, mr, torch.full_like(mr, whole)) + 1e-30
     eks, e3s = mk / den, m3 / den
-    room = bound(e3s) - eks                                # (NaN where a segment holds a NaN: caught below)
-    worst = int(torch.argmin(torch.where(torch.isnan(room), torch.full_like(room, -1.0), room)))
+    # the reported segment is the one nearest to its bound as a RATIO (a segment that holds a NaN first: caught below)
+    ratio = eks / bound(e3s)
+    worst = int(torch.argmax(torch.where(torch.isnan(ratio), torch.full_like(ratio, float("inf")), ratio)))
     REPORT.append((case, what, "segment", float(e3s[worst]), float(eks[worst]), bound(float(e3s[worst]))))
     bad = ~(eks <= bound(e3s))
     assert not bool(bad.any()), ("%s %s: %d of %d segments (%s) above the bound, first %d: error %.3e, bound %.3e"
