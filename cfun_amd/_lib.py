@@ -162,6 +162,7 @@ SAMPLE_EXPORTS = tuple(SAMPLE_SIGNATURES)
 TILE_SIGNATURES = {
     "cfun_conv3d_fwd_tile": (C.c_int, [_PP, C.POINTER(C.c_int32)]),
     "cfun_conv3d_wgrad_tile": (C.c_int, [_PP, C.POINTER(C.c_int32)]),
+    "cfun_conv3d_bwd_kernels": (C.c_int, [_PP, C.POINTER(C.c_int32)]),
 }
 TILE_EXPORTS = tuple(TILE_SIGNATURES)
 

@@ -185,7 +185,7 @@ bool make_dgrad_params(const CfunConv3dParams* p, CfunConv3dParams* q) {
 // depth-to-space epilogue:  dx[2z+p] = sum_{a in {0,1}} g[z+a] * W[t(p,a)],  t(0,0)=1, t(1,0)=2, t(1,1)=0,
 // (0,1) -> no tap.  Folded weights wd[tap'=(a,b,c)][co][(pz,py,px)*Ci + ci] are built on device from wpT.
 bool use_folded_s2_dgrad(const CfunConv3dParams* p) {
-  return CFUN_ALGO_OF(p->algo) != CFUN_ALGO_DIRECT && p->stride == 2 && !p->up2 && p->kd == 3 && p->kh == 3 && p->kw == 3 &&
+  return CFUN_ALGO_OF(p->algo) != CFUN_ALGO_DIRECT && p->stride == 2 && !p->up2 && !p->d2s && p->kd == 3 && p->kh == 3 && p->kw == 3 &&
          p->pd == 1 && p->ph == 1 && p->pw == 1 && !((p->Di | p->Hi | p->Wi) & 1) && !(p->Ci & 3) && !(p->Co & 3) &&
          p->Di == 2 * p->Do && p->Hi == 2 * p->Ho && p->Wi == 2 * p->Wo;
 }
@@ -247,8 +247,23 @@ int wgrad_nsub(const CfunConv3dParams* p, const Shape* s) {
 bool use_mfma_dgrad(const CfunConv3dParams* p, CfunConv3dParams* q, const Shape** s) {
   if (CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT) return false;
   if (!make_dgrad_params(p, q)) return false;
+  if (p->d2s) {   // the s2d gather of g: 3x3x3 only (kHasSpecial), and a lane's float4 must stay inside one parity group
+    const int cqp = p->Co >> 3, cq = p->d2s_cq > 0 ? p->d2s_cq : cqp;
+    if (!(p->kd == 3 && p->kh == 3 && p->kw == 3) || (cqp & 3) || (cq & 3)) return false;
+  }
   *s = mfma_shape(q);
   return *s != nullptr;
+}
+
+// The kernel families of the two gradients (CFUN_BWD_*, cfun_tile.h), from the predicates the launches and the workspace
+// queries ask, given their full workspaces.
+int dgrad_family(const CfunConv3dParams* p) {
+  CfunConv3dParams q;
+  const Shape* s;
+  if (use_folded_s2_dgrad(p)) return CFUN_BWD_S2FOLD;
+  if (!use_mfma_dgrad(p, &q, &s)) return CFUN_BWD_DIRECT;
+  const bool wino = !p->up2 && (p->d2s ? cfun_wino_s2d_dgrad_supported(p, &q) : cfun_wino_supported(&q));
+  return wino ? CFUN_BWD_WINO : CFUN_BWD_MFMA;
 }
 
 // y = act(scale * sum_k partial[k] + shift + res): the epilogue of a split-K conv (plain layout)
@@ -809,6 +824,16 @@ int cfun_conv3d_wgrad_tile(const CfunConv3dParams* p, int32_t out[3]) {
   if (!s) return CFUN_EINVAL;
   const int g = cfun_wino_wgrad_supported(p) ? cfun_wino_wgrad_geom(p) : wgrad_geom(p, s);
   out[0] = p->stride == 1 ? 2 : 1; out[1] = g ? 8 : 4; out[2] = g ? 8 : 16;
+  return CFUN_OK;
+}
+
+int cfun_conv3d_bwd_kernels(const CfunConv3dParams* p, int32_t out[2]) {
+  if (!out || !valid_params(p)) return CFUN_EINVAL;
+  out[0] = dgrad_family(p);
+  const bool direct = CFUN_ALGO_OF(p->algo) == CFUN_ALGO_DIRECT;
+  if (!direct && cfun_wgrad_c1_supported(p) && (int64_t)p->N * p->Do * p->Ho * p->Wo > 0) out[1] = CFUN_BWD_C1;
+  else if (direct || !wgrad_mfma_fits(p) || !mfma_shape(p)) out[1] = CFUN_BWD_DIRECT;
+  else out[1] = cfun_wino_wgrad_supported(p) ? CFUN_BWD_WINO : CFUN_BWD_MFMA;
   return CFUN_OK;
 }
 

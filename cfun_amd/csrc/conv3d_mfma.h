@@ -529,7 +529,7 @@ k_conv_mfma(const float* __restrict__ x, const float* __restrict__ wp, const flo
 // how many ways to split the channel chunks so that a small volume still fills the chip (0 workspace => 1)
 inline int splitk_factor(int64_t nblk, int nchunks, const CfunConv3dParams& p, size_t ws_bytes) {
   // fewer than ~3 workgroups per CU leaves the SIMDs with a single wave each: split until ~1024 workgroups
-  if (p.d2s || nblk >= 768 || nchunks < 8) return 1;
+  if (p.d2s || nblk >= 768 || nblk <= 0 || nchunks < 8) return 1;      // (no workgroup: an empty conv, nothing to split)
   int k = nblk <= 128 ? (int)((512 + nblk - 1) / nblk) : (int)((1024 + nblk - 1) / nblk);
   if (k > nchunks / 4) k = nchunks / 4;
   if (k > 16) k = 16;

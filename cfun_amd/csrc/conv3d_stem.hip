@@ -541,6 +541,7 @@ int pointwise_staged_ch(const CfunConv3dParams* p, bool in) {
 
 int cfun_conv_pointwise_supported(const CfunConv3dParams* p) {
   if (p->kd != 1 || p->kh != 1 || p->kw != 1 || p->stride != 1 || p->up2 || p->d2s) return 0;
+  if (p->pd | p->ph | p->pw) return 0;      // k_conv_pointwise reads x at the OUTPUT voxel's index: same grids only
   if (p->Co != 8 || (p->Ci & 3)) return 0;
   return (int64_t)p->N * p->Do * p->Ho * p->Wo >= 32768;      // small volumes: the split-K MFMA path
 }

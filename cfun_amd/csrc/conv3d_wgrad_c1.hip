@@ -202,7 +202,7 @@ int dispatch_c1(const float* x, const float* g, CfunWgradDst dst, const CfunConv
 
 // 0 = shape not handled here
 int cfun_wgrad_c1_supported(const CfunConv3dParams* p) {
-  if (p->Ci != 1 || (p->Co & 3) || p->CoP > 32 || p->up2) return 0;
+  if (p->Ci != 1 || (p->Co & 3) || p->CoP > 32 || p->up2 || p->d2s) return 0;      // (g is read as a plain [N,Do,Ho,Wo,Co] tensor)
   if (p->kd == 3 && p->kh == 3 && p->kw == 3 && p->stride == 1) return 1;
   if (p->kd == 3 && p->kh == 7 && p->kw == 7 && p->stride == 2) return 2;
   if (p->kd == 5 && p->kh == 7 && p->kw == 7 && p->stride == 2) return 3;

@@ -24,6 +24,16 @@ int cfun_conv3d_fwd_tile(const CfunConv3dParams* p, int32_t out[3]);
  * Returns 0, or CFUN_EINVAL if the weight gradient of p does not run on the MFMA / Winograd weight-gradient kernels. */
 int cfun_conv3d_wgrad_tile(const CfunConv3dParams* p, int32_t out[3]);
 
+/* Which kernel family runs the two gradients of p given their full workspaces: out = {cfun_conv3d_bwd_data,
+ * cfun_conv3d_bwd_weight*}, the counterpart of cfun_conv3d_fwd_kernel, answered by the predicates the launches ask.
+ * Returns 0, or CFUN_EINVAL for parameters the library refuses. */
+#define CFUN_BWD_DIRECT 0      /* generic VALU kernels (conv3d_direct.hip); under CFUN_ALGO_MFMA the weight gradient refuses instead */
+#define CFUN_BWD_MFMA 1        /* data gradient: k_conv_mfma on the mirrored conv; weight gradient: k_wgrad_mfma / k_wgrad_fused */
+#define CFUN_BWD_WINO 2        /* k_conv_wino on the mirrored conv / k_wgrad_wino */
+#define CFUN_BWD_S2FOLD 3      /* data gradient of a 3x3x3 stride-2 conv as one folded 2x2x2 conv with a depth-to-space epilogue */
+#define CFUN_BWD_C1 4          /* weight gradient of the C_in = 1 stems (k_wgrad_c1_mfma) */
+int cfun_conv3d_bwd_kernels(const CfunConv3dParams* p, int32_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

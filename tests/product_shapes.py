@@ -73,6 +73,17 @@ def signature(needs, x, wp, scale, shift, res, w_src, call):
                oidhw=int(w_src is not None), shift_scaled=int(bool(call.shift_scaled)))
 
 
+def case_sig(n, dhw, ci, co, k, stride=1, pad=None, up2=False, act=ACT_NONE, scale=False, shift=False, res=False,
+             res_up2=False, per_n=False, algo=0, d2s=False, d2s_cq=0, pro=PRO_NONE):
+    """A signature written by hand (the emulator tier's reference checks, tests/dispatch_cases.py): an OIDHW weight, every
+    gradient its operands can take."""
+    pad = tuple(pad) if pad is not None else tuple(kk // 2 for kk in k)
+    return Sig(n=n, dhw=tuple(dhw), ci=ci, co=co, cop=(co + 15) // 16 * 16, k=tuple(k), stride=stride, pad=pad, up2=int(up2),
+               d2s=int(d2s), d2s_cq=int(d2s_cq), tap_skip=0, res_up2=int(res_up2 and res), act=act,
+               scale_mode=0 if not scale else (2 if per_n else 1), has_shift=int(shift), res_mode=int(res), algo=algo,
+               pro=pro, stats=0, need=(True, True, bool(shift), bool(res)), oidhw=1, shift_scaled=0)
+
+
 def sig_id(s):
     """A readable, stable test id: k333_s1_4x96x96x96_40to40_lrelu_res_stats."""
     parts = ["k%d%d%d" % s.k, "s%d" % s.stride, "%dx%dx%dx%d" % ((s.n,) + s.dhw), "%dto%d" % (s.ci, s.co)]
@@ -560,6 +571,20 @@ def kernel_info(s):
                 kinds=tuple(WOP_NAMES.get(int(k), "?") for k in kinds) if rc == 0 else ("?", "?"),
                 ws=(int(lib.cfun_conv3d_fwd_workspace_bytes(C.byref(p))), int(lib.cfun_conv3d_bwd_data_workspace_bytes(C.byref(p))),
                     int(lib.cfun_conv3d_bwd_weight_workspace_bytes(C.byref(p)))))
+
+
+BWD_NAMES = {0: "direct", 1: "mfma", 2: "wino", 3: "s2fold", 4: "c1"}
+
+
+def bwd_kernels(s):
+    """(data-gradient family, weight-gradient family) of this conv (cfun_conv3d_bwd_kernels), and whether the weight-gradient
+    tile query answers (it refuses exactly the C_in = 1 and direct weight gradients)."""
+    lib = _lib.load()
+    p = ops._params(_spec(s), (s.n,) + s.dhw + (s.ci,), bool(s.scale_mode), bool(s.has_shift), bool(s.res_mode))
+    out, tile = (C.c_int32 * 2)(), (C.c_int32 * 3)()
+    _lib.check(lib.cfun_conv3d_bwd_kernels(C.byref(p), out), "conv3d_bwd_kernels")
+    return dict(dgrad=BWD_NAMES.get(int(out[0]), "?"), wgrad=BWD_NAMES.get(int(out[1]), "?"),
+                wgrad_tile=int(lib.cfun_conv3d_wgrad_tile(C.byref(p), tile)) == 0)
 
 
 def replay(s, device, algo=None):

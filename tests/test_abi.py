@@ -130,6 +130,60 @@ def test_conv_kernel_selection(emu):
     assert plan((4, 96, 96, 96, 20), co=20, **k3)[0] != 0                      # not a Winograd launch
 
 
+def test_tile_header_matches_binding(monkeypatch):
+    """include/cfun_tile.h (the tile queries and cfun_conv3d_bwd_kernels) is bound one to one by _lib.TILE_SIGNATURES and every
+    entry is exported by the built library."""
+    from cfun_amd import _lib
+    txt = open(os.path.join(ROOT, "include", "cfun_tile.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    names = sorted(set(re.findall(r"\b(cfun_[a-z0-9_]+)\s*\(", txt)))
+    assert names == sorted(_lib.TILE_EXPORTS) and "cfun_conv3d_bwd_kernels" in names
+    assert not set(names) & set(_lib.EXPORTS)
+    monkeypatch.delenv("CFUN_LIB_PATH", raising=False)
+    if not os.path.exists(_lib.DEFAULT_LIB):
+        import __graft_entry__ as ge
+        ge.build()
+    lib = ctypes.CDLL(_lib.DEFAULT_LIB)
+    for name in names:
+        assert hasattr(lib, name), name
+
+
+def test_conv_backward_kernel_selection(emu):
+    """cfun_conv3d_bwd_kernels, the counterpart of cfun_conv3d_fwd_kernel for the two gradients, at the benchmarked shapes and
+    at the shapes whose predicates admitted convs their kernels do not implement (tests/dispatch_cases.py).  Host-side logic
+    only (no launch)."""
+    import ctypes as C
+    from cfun_amd import _lib, ops
+    lib = _lib.load()
+    DIRECT, MFMA, WINO, S2FOLD, C1 = 0, 1, 2, 3, 4
+
+    def kern(shape, **spec):
+        p = ops._params(ops.ConvSpec(**spec), shape, False, False, False)
+        out = (C.c_int32 * 2)()
+        assert int(lib.cfun_conv3d_bwd_kernels(C.byref(p), out)) == 0
+        return int(out[0]), int(out[1])
+
+    k3 = dict(k=(3, 3, 3), pad=(1, 1, 1))
+    assert kern((4, 96, 96, 96, 40), co=40, **k3) == (WINO, WINO)                       # conv_norm_lrelu_l4.0
+    assert kern((4, 96, 96, 96, 20), co=20, **k3) == (MFMA, MFMA)
+    assert kern((4, 96, 96, 96, 20), co=40, stride=2, **k3) == (S2FOLD, MFMA)
+    assert kern((4, 95, 96, 96, 20), co=40, stride=2, **k3) == (DIRECT, MFMA)           # an odd extent: no fold
+    assert kern((4, 96, 96, 96, 1), co=20, **k3) == (DIRECT, C1)
+    assert kern((4, 96, 96, 96, 40), co=8, k=(1, 1, 1), pad=(0, 0, 0)) == (MFMA, MFMA)
+    assert kern((1, 8, 8, 8, 3), co=5, **k3) == (DIRECT, DIRECT)
+    assert kern((4, 96, 96, 96, 40), co=40, algo=_lib.ALGO_DIRECT, **k3) == (DIRECT, DIRECT)
+    assert kern((4, 48, 48, 48, 40), co=8 * 32, d2s=True, d2s_cq=20, tap_skip=True, **k3) == (MFMA, MFMA)   # folded up-conv
+    # depth-to-space: the C_in = 1 weight gradient and the folded stride-2 data gradient read g as a plain tensor, the s2d
+    # gather of the MFMA data gradient exists for 3x3x3 with whole channel quads per parity only
+    assert kern((1, 5, 6, 18, 1), co=16, d2s=True, **k3) == (DIRECT, DIRECT)
+    assert kern((1, 8, 8, 12, 4), co=64, stride=2, d2s=True, **k3) == (DIRECT, MFMA)
+    assert kern((1, 4, 5, 6, 8), co=32, k=(1, 1, 1), pad=(0, 0, 0), d2s=True) == (DIRECT, MFMA)
+    assert kern((1, 4, 5, 6, 8), co=48, d2s=True, **k3) == (DIRECT, DIRECT)
+    p = ops._params(ops.ConvSpec(co=16, stride=2, **k3), (1, 8, 8, 8, 8), False, False, False)
+    p.stride = 3
+    assert int(lib.cfun_conv3d_bwd_kernels(C.byref(p), (C.c_int32 * 2)())) == -1         # refused parameters
+
+
 def _gfx950_code_objects(path):
     """The gfx950 ELF images inside a HIP shared library: every clang offload bundle of its .hip_fatbin section."""
     import struct

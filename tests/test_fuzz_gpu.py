@@ -58,7 +58,11 @@ def test_roi_align_fuzz(gpu, seed):
 @pytest.mark.parametrize("seed", range(24))
 def test_conv_dispatch_fuzz(gpu, seed):
     """Forward, data-gradient and weight-gradient of randomly drawn convolutions (every kernel shape of the path, odd
-    spatial sizes, channel counts in {4..84} incl. 20 / 40 / 8, random epilogues) against torch on the CPU."""
+    spatial sizes, channel counts in {4..84} incl. 20 / 40 / 8, random epilogues) against torch on the CPU.
+
+    The stride-2 draws round every extent up to even on purpose: only then does the 3x3x3 data gradient run as the folded
+    2x2x2 conv (use_folded_s2_dgrad), the path the training step takes.  Odd extents -- the direct data gradient and the
+    high-side bound tests of the stride-2 staging -- are drawn by test_conv_dispatch_fuzz_odd_stride2 below."""
     rng = np.random.default_rng(300 + seed)
     k, stride = [((3, 3, 3), 1), ((3, 3, 3), 2), ((1, 1, 1), 1), ((1, 1, 1), 2), ((1, 3, 3), 1), ((3, 1, 1), 1),
                  ((3, 3, 3), 1), ((3, 3, 3), 1)][seed % 8]
@@ -79,6 +83,33 @@ def test_conv_dispatch_fuzz(gpu, seed):
         kw["res"] = True
     kw["act"] = int(rng.choice([kc.ACT_NONE, kc.ACT_RELU, kc.ACT_LRELU]))
     kc.check_conv(gpu, n, dhw, ci, co, k, tol=1e-4, **kw)
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_conv_dispatch_fuzz_odd_stride2(gpu, seed):
+    """The stride-2 draws of test_conv_dispatch_fuzz with at least one odd extent (all three odd on the even seeds): the last
+    output of an odd axis reads up to the input's last plane and one past it, so the high-side bound test of the staging
+    decides, and the 3x3x3 data gradient runs on the direct kernel.  Same tolerance."""
+    rng = np.random.default_rng(500 + seed)
+    k = [(3, 3, 3), (1, 1, 1)][seed % 2]
+    ci = int(rng.choice([4, 8, 12, 16, 20, 36, 40, 64, 84]))
+    co = int(rng.choice([4, 8, 16, 20, 24, 40, 48, 80]))
+    dhw = [int(v) for v in rng.integers(3, 19, 3)]
+    odd_axes = range(3) if seed % 4 < 2 else [int(rng.integers(0, 3))]
+    for ax in odd_axes:
+        dhw[ax] |= 1
+    n = int(rng.choice([1, 2, 3]))
+    kw = dict(stride=2, algo=kc.ALGO_AUTO, seed=seed)
+    if k == (1, 1, 1):
+        kw["pad"] = (0, 0, 0)
+    if rng.random() < 0.5:
+        kw.update(scale=True, per_n=bool(rng.random() < 0.5))
+    if rng.random() < 0.5:
+        kw["shift"] = True
+    if rng.random() < 0.4:
+        kw["res"] = True
+    kw["act"] = int(rng.choice([kc.ACT_NONE, kc.ACT_RELU, kc.ACT_LRELU]))
+    kc.check_conv(gpu, n, tuple(dhw), ci, co, k, tol=1e-4, **kw)
 
 
 @pytest.mark.parametrize("seed", range(4))

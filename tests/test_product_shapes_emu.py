@@ -21,13 +21,7 @@ from cfun_amd._lib import ACT_NONE, ALGO_AUTO, ALGO_DIRECT
 REF_TOL = 1e-12
 
 
-def _case_sig(n, dhw, ci, co, k, stride=1, pad=None, up2=False, act=ACT_NONE, scale=False, shift=False, res=False,
-              res_up2=False, per_n=False, algo=ALGO_AUTO, d2s=False):
-    pad = tuple(pad) if pad is not None else tuple(kk // 2 for kk in k)
-    return ps.Sig(n=n, dhw=tuple(dhw), ci=ci, co=co, cop=(co + 15) // 16 * 16, k=tuple(k), stride=stride, pad=pad, up2=int(up2),
-                  d2s=int(d2s), d2s_cq=0, tap_skip=0, res_up2=int(res_up2 and res), act=act,
-                  scale_mode=0 if not scale else (2 if per_n else 1), has_shift=int(shift), res_mode=int(res), algo=algo,
-                  pro=ps.PRO_NONE, stats=0, need=(True, True, bool(shift), bool(res)), oidhw=1, shift_scaled=0)
+_case_sig = ps.case_sig
 
 
 @pytest.mark.parametrize("name", sorted(kc.CONV_CASES))
