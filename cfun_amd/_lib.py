@@ -192,6 +192,17 @@ SURFACE_SIGNATURES = {
 }
 SURFACE_EXPORTS = tuple(SURFACE_SIGNATURES)
 
+# The lesion-scoring entries (include/cfun_lesion.h): a table of their own, for the same reason; checked by
+# tests/test_lesion_*.py.  One row of cfun_cc_rank's table is LESION_FIELDS int64 values.
+LESION_MAX_CAP = 4095
+LESION_FIELDS = 9
+LESION_SIGNATURES = {
+    "cfun_lesion_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "cfun_cc_rank": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "cfun_rank_overlap": (C.c_int, [_P, _P, _P, _I, _I, _P, _P, _Z, _P]),
+}
+LESION_EXPORTS = tuple(LESION_SIGNATURES)
+
 _lib = None
 _lib_path = None
 _is_emulator = False
@@ -213,7 +224,8 @@ def load():
             "`make -C cfun_amd/csrc -j8` or `python -c 'import __graft_entry__ as g; g.build()'`." % path)
     lib = C.CDLL(path)
     for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()) + \
-            list(EVAL_SIGNATURES.items()) + list(CC_SIGNATURES.items()) + list(SURFACE_SIGNATURES.items()):
+            list(EVAL_SIGNATURES.items()) + list(CC_SIGNATURES.items()) + list(SURFACE_SIGNATURES.items()) + \
+            list(LESION_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -12,6 +12,7 @@
                       per class left on the device (cfun_surface_stats)
     SurfaceScores     Hausdorff, HD95, ASSD and RMSD from those records, in float64 (the reference has no such scores: the
                       pin is tests/surface_ref.py)
+    lesion scores     ``run_test(lesions=...)``: lesion-level recall, precision and F1 (cfun_amd/lesions.py) and the tumour burden
 
 The reference builds two float64 one-hot arrays [H,W,D,C-1] per case, casts them to float32 and takes the diagonal of a
 [C-1,V] x [V,C-1] product; every figure it prints is a function of the (K+1)^2 integer counts computed here.  The scoring path
@@ -24,7 +25,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, model, nifti, ops
+from . import _lib, lesions as lesions_mod, model, nifti, ops
 from ._lib import check, ptr, stream, workspace
 from .ops import ptr_raw
 
@@ -306,7 +307,34 @@ def _draw_box_edges(m, roi, value=10):
             m[y, x, z1:z2] = value
 
 
-def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess=None, surface=None):
+def _lesion_settings(lesions, num_classes):
+    """run_test's ``lesions`` argument -> None, or the keyword arguments of ``lesions.lesion_scores``."""
+    if lesions is None:
+        return None
+    opts = dict(lesions) if isinstance(lesions, dict) else {"cls": lesions}
+    unknown = set(opts) - {"cls", "thresholds", "connectivity", "cap"}
+    if unknown or "cls" not in opts:
+        raise ValueError("run_test: lesions must be a class id, a tuple of them, or a dict with 'cls' and optionally "
+                         "'thresholds', 'connectivity' and 'cap', got %r" % (lesions,))
+    ids = lesions_mod._class_ids("run_test", opts["cls"])
+    if any(c >= num_classes for c in ids):
+        raise ValueError("run_test: lesion class %r outside 1 .. %d" % (opts["cls"], num_classes - 1))
+    opts["cls"] = ids
+    opts["thresholds"] = tuple(float(t) for t in opts.get("thresholds", (0.0, 0.5)))
+    return opts
+
+
+def _tumour_burden(counts, ids):
+    """(label, prediction): lesion voxels / all non-zero voxels from the confusion counts; nan when a side is all zeros."""
+    rows, cols, total = counts.sum(axis=1), counts.sum(axis=0), int(counts.sum())
+    out = []
+    for sums in (rows, cols):
+        fg = total - int(sums[0])
+        out.append(float(sum(int(sums[c]) for c in ids)) / float(fg) if fg else float("nan"))
+    return out
+
+
+def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess=None, surface=None, lesions=None):
     """The loop of ``heart_main.test`` (and of ``LiTS_main.test`` when ``hot.config`` is a LiTS configuration).
 
     ``cases``: each either ``(image_path, label_path)`` -- NIfTI files read with cfun_amd.nifti -- or ``(image, label, affine)``
@@ -335,7 +363,16 @@ def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess
     with the voxel spacing taken from the label's affine (``affine_spacing``).  The dict gains ``hausdorff``, ``hd95`` (the
     chosen percentile) and ``assd``, each [n, K-1] in millimetres, and each result carries its ``SurfaceScores`` under
     ``surface_scores``.  The records are read right after the confusion counts with nothing enqueued in between: still one
-    point of synchronisation per case.  Detector-only LiTS runs skip it, as they skip the mask scores."""
+    point of synchronisation per case.  Detector-only LiTS runs skip it, as they skip the mask scores.
+
+    ``lesions``: None (the default: exactly the above), the class id that counts as "lesion" (2 for the LiTS configurations'
+    tumour), a tuple of ids that do together, or a dict ``{"cls": ..., "thresholds": (0.0, 0.5), "connectivity": 26,
+    "cap": 1023}``.  With one, ``lesions.lesion_scores`` runs on the map that is scored -- the cleaned one when ``postprocess``
+    is given -- against the label; it is enqueued before the confusion counts are read, and its buffers are read right after
+    them: still one point of synchronisation per case.  The dict gains ``lesion_recall``, ``lesion_precision`` and
+    ``lesion_f1``, each [n, len(thresholds)], ``lesion_counts`` [n, 2] (reference lesions, predicted lesions) and
+    ``tumour_burden`` [n, 2] (lesion voxels / all non-zero voxels of the label and of the prediction, from the confusion
+    counts), and each result carries its ``LesionScores`` under ``lesion_scores``.  Detector-only LiTS runs skip it too."""
     cfg = hot.config
     lits = _is_lits(cfg)
     k = int(cfg.NUM_CLASSES)
@@ -343,6 +380,8 @@ def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess
     dev = next(hot.parameters()).device
     ious, mask_ious, dices, results, saved = [], [], [], [], []
     hds, hdqs, assds = [], [], []
+    lesion_opts = _lesion_settings(lesions, k)
+    les_recall, les_precision, les_f1, les_counts, burdens = [], [], [], [], []
     if surface is not None and surface is not False:
         percentile = 95.0 if surface is True else float(surface)
         if not 0.0 <= percentile <= 100.0:
@@ -383,12 +422,21 @@ def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess
             counts = seg_confusion(pred, label_t.permute(2, 0, 1), k)
             if percentile is not None:
                 records = surface_distances(pred, label_t.permute(2, 0, 1), k, affine_spacing(affine), percentile)
+            if lesion_opts is not None:
+                lesion_buffers = lesions_mod.lesion_scores(pred, label_t.permute(2, 0, 1), **lesion_opts)
             s = SegScores(counts)
             if percentile is not None:                                # (nothing was enqueued since the counts were read)
                 ss = res["surface_scores"] = SurfaceScores(records)
                 hds.append(ss.hausdorff)
                 hdqs.append(ss.hd_percentile)
                 assds.append(ss.assd)
+            if lesion_opts is not None:
+                ls = res["lesion_scores"] = lesions_mod.LesionScores(lesion_buffers)
+                les_recall.append(ls.recall)
+                les_precision.append(ls.precision)
+                les_f1.append(ls.f1)
+                les_counts.append((ls.n_ref, ls.n_pred))
+                burdens.append(_tumour_burden(s.counts, lesion_opts["cls"]))
             ious.append(s.per_class_iou)
             mask_ious.append(s.mask_iou)
             dices.append(s.dice)
@@ -422,4 +470,10 @@ def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess
     if percentile is not None:
         for key, rows in (("hausdorff", hds), ("hd95", hdqs), ("assd", assds)):
             summary[key] = np.array(rows, dtype=np.float64).reshape(len(rows), nfg)
+    if lesion_opts is not None:
+        nt = len(lesion_opts["thresholds"])
+        for key, rows in (("lesion_recall", les_recall), ("lesion_precision", les_precision), ("lesion_f1", les_f1)):
+            summary[key] = np.array(rows, dtype=np.float64).reshape(len(rows), nt)
+        summary["lesion_counts"] = np.array(les_counts, dtype=np.int64).reshape(len(les_counts), 2)
+        summary["tumour_burden"] = np.array(burdens, dtype=np.float64).reshape(len(burdens), 2)
     return summary
