@@ -203,6 +203,13 @@ LESION_SIGNATURES = {
 }
 LESION_EXPORTS = tuple(LESION_SIGNATURES)
 
+# The hole-filling entries (include/cfun_fill.h): a table of their own, for the same reason; checked by tests/test_fill_*.py.
+FILL_SIGNATURES = {
+    "cfun_fill_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "cfun_fill_holes": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+}
+FILL_EXPORTS = tuple(FILL_SIGNATURES)
+
 _lib = None
 _lib_path = None
 _is_emulator = False
@@ -225,7 +232,7 @@ def load():
     lib = C.CDLL(path)
     for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()) + \
             list(EVAL_SIGNATURES.items()) + list(CC_SIGNATURES.items()) + list(SURFACE_SIGNATURES.items()) + \
-            list(LESION_SIGNATURES.items()):
+            list(LESION_SIGNATURES.items()) + list(FILL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args
