@@ -210,6 +210,14 @@ FILL_SIGNATURES = {
 }
 FILL_EXPORTS = tuple(FILL_SIGNATURES)
 
+# The ball-morphology entries (include/cfun_morph.h): a table of their own, for the same reason; checked by tests/test_morph_*.py.
+MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
+MORPH_SIGNATURES = {
+    "cfun_morph_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "cfun_morph_apply": (C.c_int, [_P, _P, _I, _I, _I, C.c_uint32, _P, _F, _I, _I, _P, _P, _P, _Z, _P]),
+}
+MORPH_EXPORTS = tuple(MORPH_SIGNATURES)
+
 _lib = None
 _lib_path = None
 _is_emulator = False
@@ -232,7 +240,7 @@ def load():
     lib = C.CDLL(path)
     for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()) + \
             list(EVAL_SIGNATURES.items()) + list(CC_SIGNATURES.items()) + list(SURFACE_SIGNATURES.items()) + \
-            list(LESION_SIGNATURES.items()) + list(FILL_SIGNATURES.items()):
+            list(LESION_SIGNATURES.items()) + list(FILL_SIGNATURES.items()) + list(MORPH_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -247,10 +247,12 @@ def detect_original(hot, image, postprocess=None):
     device tensor (``.permute(1, 2, 0)`` is the reference's [H,W,D] mask), and ``empty``: True when nothing was detected --
     ``mask_device`` is then all zeros (the reference crashes there).
 
-    ``postprocess``: a ``components.Postprocess`` or ``components.FillHoles``, or None (the default: exactly the above).  With
+    ``postprocess``: a ``components.Postprocess``, ``components.FillHoles`` or ``morphology.Morphology``, or None (the default:
+    exactly the above).  With
     one, ``mask_device`` is the map cleaned by ``components.clean_components`` (and, with a ``FillHoles``, filled by
     ``components.fill_holes``) -- still on the device, nothing synchronised -- and the dict gains ``component_stats`` (the int64
-    device tensor: [K,3] of a ``Postprocess``, [K,5] of a ``FillHoles``) and ``mask_device_raw`` (the map as un-molded).  The
+    device tensor: [K,3] of a ``Postprocess``, [K,5] of a ``FillHoles``, two more columns after a ``Morphology``) and
+    ``mask_device_raw`` (the map as un-molded).  The
     reference has no such step."""
     lits = _is_lits(hot.config)
     if image.ndim != (3 if lits else 4):
@@ -354,7 +356,8 @@ def run_test(hot, cases, save_dir=None, draw_bbox=False, limit=None, postprocess
     ('beginning') the mask is zeros and the mask scores are skipped (the file name then starts with "detector": the fork's
     box-IoU figure is not computed here).
 
-    ``postprocess``: a ``components.Postprocess`` or ``components.FillHoles`` handed to ``detect_original``, or None (the
+    ``postprocess``: a ``components.Postprocess``, ``components.FillHoles`` or ``morphology.Morphology`` handed to
+    ``detect_original``, or None (the
     default: exactly the above).  With one, the cleaned (and filled) map is what is scored, drawn into and saved; each result dict carries ``component_stats`` and
     ``mask_device_raw``.  The step adds no synchronisation -- still one per case -- and the statistics stay on the device
     until the caller reads them.
