@@ -158,6 +158,14 @@ SAMPLE_SIGNATURES = {
 }
 SAMPLE_EXPORTS = tuple(SAMPLE_SIGNATURES)
 
+# The LiTS sample entries (include/cfun_sample_lits.h): a table of their own, for the same reason (tests/test_sample_emu.py
+# holds SAMPLE_EXPORTS to cfun_sample.h symbol for symbol); checked by tests/test_sample_lits_*.py.
+LITS_SAMPLE_SIGNATURES = {
+    "cfun_sample_lits_workspace_bytes": (_Z, [_P]),
+    "cfun_sample_lits": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+}
+LITS_SAMPLE_EXPORTS = tuple(LITS_SAMPLE_SIGNATURES)
+
 # The output-tile query (include/cfun_tile.h): a host-side query in a table of its own, for the same reason.
 TILE_SIGNATURES = {
     "cfun_conv3d_fwd_tile": (C.c_int, [_PP, C.POINTER(C.c_int32)]),
@@ -238,7 +246,8 @@ def load():
             "cfun_amd: %s not found -- the HIP library is required (no CPU fallback). Build it with "
             "`make -C cfun_amd/csrc -j8` or `python -c 'import __graft_entry__ as g; g.build()'`." % path)
     lib = C.CDLL(path)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()) + \
+    for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(LITS_SAMPLE_SIGNATURES.items()) + \
+            list(TILE_SIGNATURES.items()) + \
             list(EVAL_SIGNATURES.items()) + list(CC_SIGNATURES.items()) + list(SURFACE_SIGNATURES.items()) + \
             list(LESION_SIGNATURES.items()) + list(FILL_SIGNATURES.items()) + list(MORPH_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly

@@ -5,6 +5,8 @@
 //   (b) k_box_finish     partials -> utils.extract_bboxes' box, the 5 % expansion (model.py:1059-1075), the empty flag
 //   (c) k_rpn_*          build_rpn_targets (model.py:1090-1181): IoU in double, arg-max per anchor and per GT, the match rule,
 //                        the two subsamplings as a (key, index) radix select, the deltas of the kept positives
+//   (d) k_lits_gather    the LiTS fork's sample (include/cfun_sample_lits.h): normalise, zero frame, per-slice affine map,
+//                        nearest resize, re-layout, label cast and the partials of (b) in one gather pass over the output
 // Every grid-wide result goes through per-workgroup partials and a finish launch; the only atomics are integer adds on LDS
 // histograms, so every output is repeatable bit for bit.  Built without FMA contraction: the rotation's source index and the
 // IoU comparisons are exact contracts with tests/sample_ref.py (same double operations in the same order).
@@ -26,6 +28,7 @@
 
 #include "common.h"
 #include "../../include/cfun_sample.h"
+#include "../../include/cfun_sample_lits.h"
 
 namespace {
 
@@ -186,6 +189,131 @@ k_box_finish(const int32_t* __restrict__ partials, int n, int H, int W, int D, i
     }
     *empty = none;
   }
+}
+
+// ------------------------------------------------------------------------------- the LiTS sample (cfun_sample_lits.h)
+// Dataset.__getitem__ of the fork (LiTS_2017/model.py:1145-1248) as one gather: every output voxel of normalise -> centre in
+// the zero frame -> rotate per slice -> nearest-resize depends on exactly one source voxel, so the 646x646x536 frames are
+// never built.  k_rotate_relay's tile carries over (one output row y, 64 x, 64 z; columns through the [64][65] LDS tile; rows
+// out as 16-byte stores); new is that the source z of each of the 64 output z is a map as well, computed once per workgroup
+// next to the 64 source pixels.  Each lane READS ITS OWN STRIDED ELEMENT along z (stride P_D / D', about 2.1 at the product
+// shape) rather than the contiguous run followed by a select: the stride stays far below a 32-byte sector, so both forms pull
+// the same sectors from HBM, and the direct read needs no run buffer whose length depends on the ratio (an up-sampling
+// shares one source z among several lanes; a steep down-sampling would need a run of any length).  What the stride costs
+// is sectors fetched per byte used -- a measurement (profiles/sample_lits_pipeline.txt), not hidden by either form.
+struct LitsArgs {
+  int64_t is[3], ls[3];      // element strides of image / label along H, W, D
+  int n[3];                  // source extent H, W, D
+  int P[3];                  // frame extent
+  int off[3];                // the source's position in the frame
+  int m[3];                  // output extent H', W', D'
+  double map[6];
+  int has_map, normalise, lab_bytes;
+};
+
+// cfun_resize3d's order-0 index (resize.hip)
+__device__ __forceinline__ int frame_index(int o, int P, int m) {
+  const int k = (int)floor(((double)o + 0.5) * ((double)P / (double)m));
+  return k < 0 ? 0 : (k > P - 1 ? P - 1 : k);
+}
+
+// (long long)(v > 0 ? v + 0.5 : v - 0.5), kept in double: the range test comes before any cast
+__device__ __forceinline__ double round_half_away(double v) { return trunc(v > 0.0 ? v + 0.5 : v - 0.5); }
+
+__global__ void __launch_bounds__(kNT)
+k_lits_gather(const float* __restrict__ img, const void* __restrict__ lab, float* __restrict__ oimg, uint8_t* __restrict__ olab,
+              int32_t* __restrict__ partials, LitsArgs a, int vec) {
+  __shared__ float timg[kTZ * kPitch];
+  __shared__ int tlab[kTZ * kPitch];
+  __shared__ long long off_i[kTX], off_l[kTX];
+  __shared__ int src_z[kTZ];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int x0 = blockIdx.x * kTX, y = blockIdx.y, z0 = blockIdx.z * kTZ;
+  const int Hs = a.n[0], Ws = a.n[1], Ds = a.n[2], Ho = a.m[0], Wo = a.m[1], Do = a.m[2];
+
+  if (t < kTX) {                       // the source pixel of each output x of this row: once per workgroup, in double
+    const int x = x0 + t;
+    long long oi = kOutside, ol = kOutside;
+    if (x < Wo) {
+      const double fx = (double)frame_index(x, a.P[1], Wo), fy = (double)frame_index(y, a.P[0], Ho);
+      double col = fx, row = fy;
+      if (a.has_map) {
+        col = round_half_away(a.map[0] * fx + a.map[1] * fy + a.map[2]);
+        row = round_half_away(a.map[3] * fx + a.map[4] * fy + a.map[5]);
+      }
+      if (col >= 0.0 && col < (double)a.P[1] && row >= 0.0 && row < (double)a.P[0]) {
+        const long long ix = (long long)col - a.off[1], iy = (long long)row - a.off[0];
+        if (ix >= 0 && ix < Ws && iy >= 0 && iy < Hs) {
+          oi = iy * a.is[0] + ix * a.is[1];
+          ol = iy * a.ls[0] + ix * a.ls[1];
+        }
+      }
+    }
+    off_i[t] = oi;
+    off_l[t] = ol;
+  } else if (t < kTX + kTZ) {          // the source z of each output z of this tile: once per workgroup as well
+    const int zo = z0 + (t - kTX);
+    int sz = -1;
+    if (zo < Do) {
+      const int f = frame_index(zo, a.P[2], Do) - a.off[2];
+      if (f >= 0 && f < Ds) sz = f;
+    }
+    src_z[t - kTX] = sz;
+  }
+  __syncthreads();
+
+  const int z = z0 + lane;
+  const int sz = src_z[lane];
+  const long long zi = (long long)sz * a.is[2], zl = (long long)sz * a.ls[2];
+  int mm[6] = {INT_MAX, -1, INT_MAX, -1, INT_MAX, -1};
+  for (int xi = wave; xi < kTX; xi += kNT / 64) {
+    const long long oi = off_i[xi], ol = off_l[xi];
+    float v = 0.f;
+    int l = 0;
+    if (sz >= 0 && oi != kOutside) {
+      v = img[oi + zi];
+      l = a.lab_bytes == 1 ? (int)static_cast<const uint8_t*>(lab)[ol + zl] : (static_cast<const int32_t*>(lab)[ol + zl] & 255);
+      if (a.normalise) {
+        v = __fdiv_rn(__fsub_rn(v, 300.f), -600.f);
+        v = v > 1.f ? 1.f : (v < 0.f ? 0.f : v);
+      }
+    }
+    timg[lane * kPitch + xi] = v;
+    tlab[lane * kPitch + xi] = l;
+    if (l != 0) {
+      const int x = x0 + xi;
+      mm[0] = z < mm[0] ? z : mm[0]; mm[1] = z > mm[1] ? z : mm[1];
+      mm[2] = y; mm[3] = y;
+      mm[4] = x < mm[4] ? x : mm[4]; mm[5] = x > mm[5] ? x : mm[5];
+    }
+  }
+  __syncthreads();
+
+  if (vec) {                           // W' % 4 == 0, 16-byte aligned outputs: a quad of x per lane
+    const int x4 = (t & 15) * 4;
+    if (x0 + x4 < Wo) {
+      for (int zz = t >> 4; zz < kTZ; zz += kNT / 16) {
+        const int zo = z0 + zz;
+        if (zo >= Do) break;
+        const long long o = ((long long)zo * Ho + y) * Wo + x0 + x4;
+        const float* r = timg + zz * kPitch + x4;
+        const int* q = tlab + zz * kPitch + x4;
+        *reinterpret_cast<float4*>(oimg + o) = make_float4(r[0], r[1], r[2], r[3]);
+        *reinterpret_cast<uint32_t*>(olab + o) = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+      }
+    }
+  } else if (x0 + lane < Wo) {
+    for (int zz = wave; zz < kTZ; zz += kNT / 64) {
+      const int zo = z0 + zz;
+      if (zo >= Do) break;
+      const long long o = ((long long)zo * Ho + y) * Wo + x0 + lane;
+      oimg[o] = timg[zz * kPitch + lane];
+      olab[o] = (uint8_t)tlab[zz * kPitch + lane];
+    }
+  }
+
+  const int wg = ((int)blockIdx.z * (int)gridDim.y + (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x;
+  block_minmax6(mm, partials + (long long)wg * 6);
 }
 
 // ------------------------------------------------------------------------------------------------------- RPN targets
@@ -468,6 +596,48 @@ extern "C" int cfun_sample_rpn_targets(const float* anchors, int32_t A, const fl
   CFUN_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_rpn_select, dim3(1), dim3(kNT), 0, st, rpn_match, keys, anchors, gt_boxes, (const int32_t*)iou_arg, rpn_bbox,
                      counts, s);
+  CFUN_LAUNCH_CHECK();
+  return CFUN_OK;
+}
+
+extern "C" size_t cfun_sample_lits_workspace_bytes(const int32_t* out_dims) {
+  if (!out_dims || out_dims[0] <= 0 || out_dims[1] <= 0 || out_dims[2] <= 0) return 0;
+  return rotate_workgroups(out_dims[0], out_dims[1], out_dims[2]) * 6 * sizeof(int32_t);
+}
+
+extern "C" int cfun_sample_lits(const float* image, const int64_t* image_strides, const void* label, const int64_t* label_strides,
+                                int32_t label_elem_size, const int32_t* dims, const int32_t* frame, const int32_t* offset,
+                                const int32_t* out_dims, const double* map, int32_t normalise, float* out_image,
+                                uint8_t* out_label, int32_t* raw_box, int32_t* box, int32_t* empty, void* workspace,
+                                size_t workspace_bytes, cfun_stream_t stream) {
+  if (!image || !label || !image_strides || !label_strides || !dims || !frame || !offset || !out_dims || !out_image ||
+      !out_label || !raw_box || !box || !empty)
+    return CFUN_EINVAL;
+  if (label_elem_size != 1 && label_elem_size != 4) return CFUN_EINVAL;
+  LitsArgs a;
+  for (int d = 0; d < 3; ++d) {
+    a.is[d] = image_strides[d]; a.ls[d] = label_strides[d];
+    a.n[d] = dims[d]; a.P[d] = frame[d]; a.off[d] = offset[d]; a.m[d] = out_dims[d];
+    if (a.n[d] <= 0 || a.P[d] <= 0 || a.m[d] <= 0 || a.off[d] < 0 || (int64_t)a.off[d] + a.n[d] > (int64_t)a.P[d]) return CFUN_EINVAL;
+  }
+  a.has_map = map != nullptr;
+  for (int k = 0; k < 6; ++k) {
+    a.map[k] = map ? map[k] : 0.0;
+    if (!isfinite(a.map[k])) return CFUN_EINVAL;
+  }
+  a.normalise = normalise != 0;
+  a.lab_bytes = label_elem_size;
+  const int Ho = a.m[0], Wo = a.m[1], Do = a.m[2];
+  const size_t nwg = rotate_workgroups(Ho, Wo, Do);
+  if (Ho > 65535 || (size_t)((Do + kTZ - 1) / kTZ) > 65535 || nwg > (size_t)INT_MAX / 6) return CFUN_EINVAL;
+  if (!workspace || workspace_bytes < nwg * 6 * sizeof(int32_t)) return CFUN_EWORKSPACE;
+  int32_t* partials = (int32_t*)workspace;
+  const int vec = (Wo % 4 == 0) && cfun_aligned16(out_image) && (((uintptr_t)out_label) & 3) == 0;
+  hipLaunchKernelGGL(k_lits_gather, dim3((unsigned)((Wo + kTX - 1) / kTX), (unsigned)Ho, (unsigned)((Do + kTZ - 1) / kTZ)), dim3(kNT),
+                     0, cfun_st(stream), image, label, out_image, out_label, partials, a, vec);
+  CFUN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_box_finish, dim3(1), dim3(kNT), 0, cfun_st(stream), (const int32_t*)partials, (int)nwg, Ho, Wo, Do, raw_box,
+                     box, empty);
   CFUN_LAUNCH_CHECK();
   return CFUN_OK;
 }

@@ -5,6 +5,11 @@
     build_rpn_targets   model.build_rpn_targets (model.py:1090-1181)                         -- cfun_sample_rpn_targets
     load_image_gt       both plus utils.mold_image and the class tiling: the dict ``train.train_epoch`` consumes
     make_sample         utils.resize_image / resize_mask (mode 'self') in front of load_image_gt
+    frame_rotate_resize the LiTS fork's Dataset.__getitem__ (LiTS_2017/model.py:1145-1248) up to load_image_gt: clamp-normalise,
+                        centre in the zero PAD_IMAGE_SHAPE frame, rotate per slice, nearest-resize to IMAGE_SHAPE, box -- one
+                        gather pass, the frame never built                                  -- cfun_sample_lits
+    make_sample_lits    frame_rotate_resize plus the RPN targets, window and image_meta: the fork's training sample
+    draw_angle          the fork's integer rotation angle, drawn on the host as the fork draws it
 
 Nothing on this path waits for the device: box, tiling and counts stay device tensors.  Only ``strict=True`` reads back (the
 empty flag and the label range) and raises where the reference would.
@@ -22,6 +27,7 @@ voxel along edges.
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _lib, utils
@@ -132,3 +138,94 @@ def make_sample(image_hwd, mask_hwd, angle, config, anchors, keys=None, strict=F
     image = utils.resize_image(image[..., None].to(torch.float32), min_dim=mn, max_dim=mx, mode="self", device=dev)[0]
     mask = utils.resize_mask(mask, None, None, max_dim=mx, min_dim=mn, mode="self", device=dev)
     return load_image_gt(image, mask, angle, config, anchors, keys=keys, strict=strict)
+
+
+# ------------------------------------------------------------------------------------------------------ the LiTS fork's sample
+def rotation_map(angle, frame_h, frame_w):
+    """The six doubles (m00 m01 m02 m10 m11 m12) of cfun_sample_lits.h for a rotation by ``angle`` degrees about the centre of a
+    [frame_h, frame_w] slice: skimage.transform.rotate's translate(centre) . rotate . translate(-centre), used as the inverse map
+    (rows = H, cols = W)."""
+    t = math.radians(float(angle))
+    c, s = math.cos(t), math.sin(t)
+    cx, cy = frame_w / 2 - 0.5, frame_h / 2 - 0.5
+    return (c, -s, cx - c * cx + s * cy, s, c, cy - s * cx - c * cy)
+
+
+def frame_rotate_resize(image, mask, frame, out_shape, angle=None, normalise=True, strict=False):
+    """image float32 / mask int8, uint8 or int32, both [H,W,D] with any strides (the loader's arrays, read in place; no conversion
+    pass over the label).  The pair is centred in a virtual zero ``frame`` (PH, PW, PD) -- offset ``int((P - n) / 2.0)`` per axis
+    as the reference computes it --, every [PH,PW] slice is rotated by the integer or float ``angle`` in degrees (``None``: no map,
+    the fork's validation form; bit-identical to angle 0), and the frame is nearest-resized to ``out_shape`` (H', W', D').
+    ``normalise``: the fork's preprocess_image on the source values, (x - 300) / (-600) clamped to [0, 1] with IEEE float32
+    operations (cfun_sample_lits.h step 5: utils.preprocess_image_lits on the host, within 1 ulp of it on the device, where
+    torch multiplies by the reciprocal); the frame's zeros stay zeros.  Returns (image [D',H',W']
+    float32, labels [D',H',W'] uint8, raw_box int32[6], box int32[6], empty int32[1]) on the device.  Preconditions: equal shapes,
+    a source that fits the frame, label values in [0, 255] (the range is verified only with ``strict``, which reads back)."""
+    lib = _lib.load()
+    image, mask = _volume(image), _volume(mask)
+    if tuple(image.shape) != tuple(mask.shape):
+        raise ValueError("frame_rotate_resize: image %s and mask %s differ in shape" % (tuple(image.shape), tuple(mask.shape)))
+    if image.device != mask.device:
+        raise ValueError("frame_rotate_resize: image and mask sit on different devices")
+    if mask.dtype not in (torch.int8, torch.uint8, torch.int32):
+        raise ValueError("frame_rotate_resize: int8, uint8 or int32 label volume expected, got %s" % (mask.dtype,))
+    if image.dtype != torch.float32:
+        image = image.to(torch.float32)
+    n = [int(v) for v in image.shape]
+    frame = [int(v) for v in frame]
+    m = [int(v) for v in out_shape]
+    if len(frame) != 3 or len(m) != 3 or min(n + frame + m) <= 0 or m[0] > 65535:
+        raise ValueError("frame_rotate_resize: unsupported extents: source %s, frame %s, output %s" % (n, frame, m))
+    if any(k > p for k, p in zip(n, frame)):
+        raise ValueError("frame_rotate_resize: the source %s does not fit the frame %s" % (n, frame))
+    off = [int((p - k) / 2.0) for p, k in zip(frame, n)]
+    if strict:
+        lo, hi = torch.aminmax(mask)
+        if int(lo) < 0 or int(hi) > 255:
+            raise ValueError("frame_rotate_resize: label values must lie in [0, 255], got [%d, %d]" % (int(lo), int(hi)))
+    i64, i32 = C.c_int64 * 3, C.c_int32 * 3
+    ws = workspace(lib.cfun_sample_lits_workspace_bytes(i32(*m)), image)
+    out = torch.empty((m[2], m[0], m[1]), dtype=torch.float32, device=image.device)
+    labels = torch.empty((m[2], m[0], m[1]), dtype=torch.uint8, device=image.device)
+    small = torch.empty(16, dtype=torch.int32, device=image.device)
+    raw_box, box, empty = small[0:6], small[6:12], small[12:13]
+    amap = (C.c_double * 6)(*rotation_map(angle, frame[0], frame[1])) if angle is not None else None
+    check(lib.cfun_sample_lits(ptr_raw(image), i64(*image.stride()), ptr_raw(mask), i64(*mask.stride()), mask.element_size(),
+                               i32(*n), i32(*frame), i32(*off), i32(*m), amap, int(bool(normalise)), ptr(out), ptr(labels),
+                               ptr(raw_box), ptr(box), ptr(empty), ptr(ws), ws.numel(), stream(image)), "sample_lits")
+    if strict and int(empty):
+        raise ValueError("frame_rotate_resize: the label volume is empty (the reference's extract_bboxes raises here as well)")
+    return out, labels, raw_box, box, empty
+
+
+def draw_angle(config, generator=None):
+    """The fork's per-sample rotation angle: an int in [ROTATE_ANGLE[0], ROTATE_ANGLE[1]), drawn on the host with
+    ``torch.randint`` as the fork draws it (LiTS_2017/model.py:1213); ``generator``: a CPU torch.Generator to draw from."""
+    lo, hi = [int(v) for v in config.ROTATE_ANGLE]
+    return int(torch.randint(lo, hi, (1,), generator=generator))
+
+
+def make_sample_lits(image_hwd, mask_hwd, angle, config, anchors, keys=None, strict=False):
+    """The LiTS fork's training sample (Dataset.__getitem__, LiTS_2017/model.py:1145-1248) from the loader's raw [H,W,D] arrays
+    (numpy or tensors): the CT in HU, the label as int8 (what the fork stores), uint8 or int32.  ``angle``: degrees (the fork:
+    ``draw_angle(config)`` when ``config.AUGMENTATION``), ``None`` = the fork's validation form (``augmentation=False``).
+    Returns the dict ``train.train_epoch`` consumes, with load_image_gt's keys, plus ``window`` and ``image_meta`` as
+    utils.mold_inputs_lits computes them.  ``image`` [1,1,D',H',W'] is the clamp-normalised volume WITHOUT utils.mold_image:
+    the fork never z-scores its input (its mold_inputs does not either)."""
+    dev = anchors.device
+    image = _volume(torch.as_tensor(image_hwd).to(dev))
+    mask = _volume(torch.as_tensor(mask_hwd).to(dev))
+    frame = [int(v) for v in config.PAD_IMAGE_SHAPE]
+    h, w, d = [int(v) for v in config.IMAGE_SHAPE[:3]]
+    img, labels, raw_box, box, empty = frame_rotate_resize(image, mask, frame, (h, w, d), angle=angle, normalise=True, strict=strict)
+    nfg = int(config.NUM_CLASSES) - 1
+    boxf = box.to(torch.float32)[None]
+    rpn_match, rpn_bbox, counts = build_rpn_targets(anchors, boxf, config, keys)
+    sx, sy, sz = [int((p - k) / 2.0) for p, k in zip(frame, image.shape)]
+    ph, pw, pd = frame
+    window = (sz * d / pd, sx * h / ph, sy * w / pw, config.IMAGE_MIN_DIM - sz * d / pd, config.IMAGE_MAX_DIM - sx * h / ph,
+              config.IMAGE_MAX_DIM - sy * w / pw)
+    meta = utils.compose_image_meta(0, (h, w, d), window, np.zeros([config.NUM_CLASSES], dtype=np.int32))
+    return dict(image=img[None, None], gt_class_ids=torch.arange(1, nfg + 1, device=dev), gt_boxes=boxf.repeat(nfg, 1),
+                gt_labels=labels, rpn_match=rpn_match, rpn_bbox_t=rpn_bbox, raw_box=raw_box, empty=empty, rpn_counts=counts,
+                window=window, image_meta=meta)
