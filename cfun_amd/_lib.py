@@ -166,6 +166,14 @@ LITS_SAMPLE_SIGNATURES = {
 }
 LITS_SAMPLE_EXPORTS = tuple(LITS_SAMPLE_SIGNATURES)
 
+# The native-grid entries (include/cfun_native.h): a table of their own, for the same reason; checked by tests/test_native_*.py.
+ELEM_INT16, ELEM_FLOAT32, ELEM_FLOAT64 = 0, 1, 2
+NATIVE_SIGNATURES = {
+    "cfun_mold_native": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "cfun_map_resize": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+}
+NATIVE_EXPORTS = tuple(NATIVE_SIGNATURES)
+
 # The output-tile query (include/cfun_tile.h): a host-side query in a table of its own, for the same reason.
 TILE_SIGNATURES = {
     "cfun_conv3d_fwd_tile": (C.c_int, [_PP, C.POINTER(C.c_int32)]),
@@ -247,7 +255,7 @@ def load():
             "`make -C cfun_amd/csrc -j8` or `python -c 'import __graft_entry__ as g; g.build()'`." % path)
     lib = C.CDLL(path)
     for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(LITS_SAMPLE_SIGNATURES.items()) + \
-            list(TILE_SIGNATURES.items()) + \
+            list(NATIVE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()) + \
             list(EVAL_SIGNATURES.items()) + list(CC_SIGNATURES.items()) + list(SURFACE_SIGNATURES.items()) + \
             list(LESION_SIGNATURES.items()) + list(FILL_SIGNATURES.items()) + list(MORPH_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly

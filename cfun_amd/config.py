@@ -112,6 +112,7 @@ class LiTSConfig(Config):
     LOSS_WEIGHTS = {"rpn_class_loss": 50., "rpn_bbox_loss": 5., "mrcnn_class_loss": 50., "mrcnn_bbox_loss": 5.,
                     "mrcnn_mask_loss": 2., "mrcnn_mask_edge_loss": 0.25}     # LiTS_2017/LiTS_main.py:162-169
     PAD_IMAGE_SHAPE = [646, 646, 536]   # LiTS_2017/LiTS_main.py:121: every volume is centred in this zero frame, then resized
+    MEAN_SPACING = (0.79272507, 0.79272507, 1.50625819)   # LiTS_2017/preprocessing.py:6: every volume is resampled to this (mm)
     AUGMENTATION = True                 # LiTS_2017/LiTS_main.py:127: rotate every training sample per slice ...
     ROTATE_ANGLE = (-30, 31)            # ... by an integer angle from this half-open range (LiTS_2017/config.py:134)
     POST_NMS_ROIS_INFERENCE = 50        # LiTS_2017/LiTS_main.py:107

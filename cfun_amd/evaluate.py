@@ -257,9 +257,15 @@ def detect_original(hot, image, postprocess=None):
     lits = _is_lits(hot.config)
     if image.ndim != (3 if lits else 4):
         raise ValueError("detect_original: %s volume expected, got shape %s" % ("[H,W,D]" if lits else "[H,W,D,1]", tuple(image.shape)))
-    h, w, d = [int(v) for v in image.shape[:3]]
     molded, _, windows = hot.mold_inputs([image])
-    window = tuple(float(v) for v in windows[0])
+    return detect_molded(hot, molded, tuple(float(v) for v in windows[0]), [int(v) for v in image.shape[:3]], postprocess)
+
+
+def detect_molded(hot, molded, window, shape, postprocess=None):
+    """``detect_original`` behind the mold: ``predict_inference`` on ``molded`` [1,1,D',H',W'], the un-mold through ``window``
+    into a volume of ``shape`` = (h, w, d), then ``postprocess``.  ``cfun_amd.native.detect_native`` enters here with the
+    tensor it molded from the scanner's grid and the RESAMPLED shape."""
+    h, w, d = [int(v) for v in shape]
     det, masks = hot.predict_inference(molded[0:1], window)
     overlap = getattr(hot.config, "UNMOLD_OVERLAP_TILE", False)
     found = det.shape[1] > 0
