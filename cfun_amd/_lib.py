@@ -174,6 +174,15 @@ NATIVE_SIGNATURES = {
 }
 NATIVE_EXPORTS = tuple(NATIVE_SIGNATURES)
 
+# The heart sample entries (include/cfun_sample_heart.h): a table of their own, for the same reason; checked by
+# tests/test_sample_heart_*.py.  The image's elem_kind is ELEM_*; the label's kind:
+LABEL_INT8, LABEL_UINT8, LABEL_INT16, LABEL_INT32 = 0, 1, 2, 3
+HEART_SAMPLE_SIGNATURES = {
+    "cfun_sample_heart_workspace_bytes": (_Z, [_P]),
+    "cfun_sample_heart": (C.c_int, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _D, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+}
+HEART_SAMPLE_EXPORTS = tuple(HEART_SAMPLE_SIGNATURES)
+
 # The output-tile query (include/cfun_tile.h): a host-side query in a table of its own, for the same reason.
 TILE_SIGNATURES = {
     "cfun_conv3d_fwd_tile": (C.c_int, [_PP, C.POINTER(C.c_int32)]),
@@ -255,7 +264,7 @@ def load():
             "`make -C cfun_amd/csrc -j8` or `python -c 'import __graft_entry__ as g; g.build()'`." % path)
     lib = C.CDLL(path)
     for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(LITS_SAMPLE_SIGNATURES.items()) + \
-            list(NATIVE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()) + \
+            list(NATIVE_SIGNATURES.items()) + list(HEART_SAMPLE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()) + \
             list(EVAL_SIGNATURES.items()) + list(CC_SIGNATURES.items()) + list(SURFACE_SIGNATURES.items()) + \
             list(LESION_SIGNATURES.items()) + list(FILL_SIGNATURES.items()) + list(MORPH_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly

@@ -9,6 +9,9 @@
     detect_native       mold_inputs_native, predict_inference, the un-mold into the RESAMPLED shape (what ``detect`` would see
                         from the .npy), postprocess, map_resize to the image's own shape
     predict_for_submit  the loop of LiTS_main.predict_for_submit (LiTS_2017/LiTS_main.py:370-394)
+    mold_inputs_heart   the HEART configurations' mold_inputs (model.py:1774-1810) in one pass from the loader's array: order-1
+                        resize, cast back, z-score; no label, no rotation                    -- cfun_sample_heart
+    detect_heart        mold_inputs_heart, then evaluate.detect_molded into the image's own shape
 
 The rule is include/cfun_native.h's; tests/native_ref.py restates it and tests/test_native_ref.py holds the restatement to
 scipy's zoom (the code path oracle.cfun_oracle.skimage_resize stands on) bit for bit.  Nothing here waits for the device except
@@ -21,7 +24,7 @@ import re
 import numpy as np
 import torch
 
-from . import _lib, evaluate, nifti, utils
+from . import _lib, evaluate, nifti, sample, utils
 from ._lib import check, ptr, stream
 from .ops import ptr_raw
 
@@ -126,6 +129,42 @@ def detect_native(hot, image, affine, postprocess=None):
     res["resampled_shape"] = tuple(int(v) for v in rs)
     res["mask_native"] = map_resize(res["mask_device"], [int(v) for v in image.shape[:3]])
     return res
+
+
+def mold_inputs_heart(config, images, device=None):
+    """``utils.mold_inputs`` through cfun_sample_heart: every image [H,W,D,1] (numpy or tensor, its own dtype and memory order;
+    int16, float32 and float64 are read in place) -> (molded float32 [N,1,D',H',W'] on the device, image_metas, windows), the
+    same triple.  The rule is include/cfun_sample_heart.h's without a label and without a rotation; an integer image is cast
+    back to its dtype after the resize, as mold_inputs does."""
+    dev = torch.device(device) if device is not None else utils._device()
+    if config.IMAGE_RESIZE_MODE != "self":
+        raise NotImplementedError("mold_inputs_heart: IMAGE_RESIZE_MODE %r" % (config.IMAGE_RESIZE_MODE,))
+    mx, mn = int(config.IMAGE_MAX_DIM), int(config.IMAGE_MIN_DIM)
+    molded, metas, windows = [], [], []
+    for image in images:
+        if image.ndim != 4 or image.shape[3] != 1:
+            raise ValueError("mold_inputs_heart: [H,W,D,1] volume expected, got %s" % (tuple(image.shape),))
+        vol = image[..., 0]
+        # the reference casts the resized image back to the LOADER's dtype: decided before _upload widens what the kernel cannot read
+        integer = not vol.dtype.is_floating_point if torch.is_tensor(vol) else bool(np.issubdtype(np.asarray(vol).dtype, np.integer))
+        out = sample.resize_rotate_box(_upload(vol, dev), None, (mx, mx, mn), None, zscore=True, truncate=integer)[0]
+        molded.append(out[None])
+        window = (0, 0, 0, mn, mx, mx)
+        metas.append(utils.compose_image_meta(0, tuple(image.shape), window, np.zeros([config.NUM_CLASSES], dtype=np.int32)))
+        windows.append(window)
+    return torch.stack(molded), np.stack(metas), np.stack(windows)
+
+
+def detect_heart(hot, image, postprocess=None):
+    """``evaluate.detect_original`` for one raw heart volume [H,W,D,1] with the mold done by ``mold_inputs_heart``: the same
+    dict, un-molded into the image's own shape."""
+    if evaluate._is_lits(hot.config):
+        raise ValueError("detect_heart: a heart configuration is expected (the LiTS route is detect_native)")
+    if image.ndim != 4:
+        raise ValueError("detect_heart: [H,W,D,1] volume expected, got shape %s" % (tuple(image.shape),))
+    dev = next(hot.parameters()).device
+    molded, _, windows = mold_inputs_heart(hot.config, [image], device=dev)
+    return evaluate.detect_molded(hot, molded, tuple(float(v) for v in windows[0]), [int(v) for v in image.shape[:3]], postprocess)
 
 
 def _submit_case(case, index):

@@ -10,6 +10,10 @@
                         gather pass, the frame never built                                  -- cfun_sample_lits
     make_sample_lits    frame_rotate_resize plus the RPN targets, window and image_meta: the fork's training sample
     draw_angle          the fork's integer rotation angle, drawn on the host as the fork draws it
+    resize_rotate_box   the heart route from the LOADER's grid: utils.resize_image (order 1, clip, the cast back to an integer
+                        loader dtype), utils.resize_mask (order 0), the rotation, the box and utils.mold_image's z-score as one
+                        gather pass, a finish launch and a flat pass; neither resized volume built   -- cfun_sample_heart
+    make_sample_heart   resize_rotate_box plus the RPN targets: make_sample's dict
 
 Nothing on this path waits for the device: box, tiling and counts stay device tensors.  Only ``strict=True`` reads back (the
 empty flag and the label range) and raises where the reference would.
@@ -138,6 +142,89 @@ def make_sample(image_hwd, mask_hwd, angle, config, anchors, keys=None, strict=F
     image = utils.resize_image(image[..., None].to(torch.float32), min_dim=mn, max_dim=mx, mode="self", device=dev)[0]
     mask = utils.resize_mask(mask, None, None, max_dim=mx, min_dim=mn, mode="self", device=dev)
     return load_image_gt(image, mask, angle, config, anchors, keys=keys, strict=strict)
+
+
+# ------------------------------------------------------------------------------------------- the heart sample in one pass
+_HEART_ELEM = {torch.int16: _lib.ELEM_INT16, torch.float32: _lib.ELEM_FLOAT32, torch.float64: _lib.ELEM_FLOAT64}
+_HEART_LABEL = {torch.int8: _lib.LABEL_INT8, torch.uint8: _lib.LABEL_UINT8, torch.int16: _lib.LABEL_INT16, torch.int32: _lib.LABEL_INT32}
+
+
+def resize_rotate_box(image, mask, out_shape, angle, zscore=True, strict=False, truncate=None, clip=True):
+    """image [H,W,D] in the loader's dtype and memory order (int16, float32 and float64 are read in place through their strides;
+    anything else is cast to float64 on the device first), mask an integer [H,W,D] volume or ``None`` (int8, uint8, int16 and
+    int32 are read in place, other integers cast to int32), ``out_shape`` (H', W', D'), ``angle`` in degrees or ``None`` (no
+    rotation, bit-identical to angle 0).  The rule is include/cfun_sample_heart.h's: skimage's order-1 resize with its clip to
+    the source's range (``clip``; the bounds come from a device-side aminmax, nothing reads back), the reference's cast back to
+    an integer loader dtype (``truncate``; ``None``: exactly when ``image``'s dtype is an integer), the float32 cast, the
+    rotation in the resized grid, the order-0 label, the box, and with ``zscore`` utils.mold_image.  Returns (image [D',H',W']
+    float32, labels [D',H',W'] uint8, raw_box int32[6], box int32[6], empty int32[1], stats float64[2] = mean, std) on the
+    device; labels, boxes and flag are ``None`` without a mask, stats without ``zscore``."""
+    lib = _lib.load()
+    image = _volume(image)
+    integer = not (image.dtype.is_floating_point or image.dtype.is_complex)
+    if image.dtype not in _HEART_ELEM:
+        image = image.to(torch.float64)
+    if mask is not None:
+        mask = _volume(mask)
+        if tuple(image.shape) != tuple(mask.shape):
+            raise ValueError("resize_rotate_box: image %s and mask %s differ in shape" % (tuple(image.shape), tuple(mask.shape)))
+        if image.device != mask.device:
+            raise ValueError("resize_rotate_box: image and mask sit on different devices")
+        if mask.dtype.is_floating_point or mask.dtype == torch.bool:
+            raise ValueError("resize_rotate_box: integer label volume expected, got %s" % (mask.dtype,))
+        if mask.dtype not in _HEART_LABEL:
+            mask = mask.to(torch.int32)
+    n = [int(v) for v in image.shape]
+    m = [int(v) for v in out_shape]
+    if len(m) != 3 or min(n + m) <= 0 or m[0] > 65535:
+        raise ValueError("resize_rotate_box: unsupported extents: source %s, output %s" % (n, m))
+    if strict and mask is not None:
+        lo, hi = torch.aminmax(mask)
+        if int(lo) < 0 or int(hi) > 255:
+            raise ValueError("resize_rotate_box: label values must lie in [0, 255], got [%d, %d]" % (int(lo), int(hi)))
+    dev = image.device
+    bounds = None
+    if clip:
+        lo, hi = torch.aminmax(image)
+        bounds = torch.stack([lo, hi]).to(torch.float64).contiguous()        # scikit-image's clip=True: the source's own range
+    rotate = angle is not None
+    rad = math.radians(float(angle)) if rotate else 0.0
+    i64, i32 = C.c_int64 * 3, C.c_int32 * 3
+    ws = workspace(lib.cfun_sample_heart_workspace_bytes(i32(*m)), image)
+    out = torch.empty((m[2], m[0], m[1]), dtype=torch.float32, device=dev)
+    labels = raw_box = box = empty = None
+    if mask is not None:
+        labels = torch.empty((m[2], m[0], m[1]), dtype=torch.uint8, device=dev)
+        small = torch.empty(16, dtype=torch.int32, device=dev)
+        raw_box, box, empty = small[0:6], small[6:12], small[12:13]
+    stats = torch.empty(2, dtype=torch.float64, device=dev) if zscore else None
+    check(lib.cfun_sample_heart(ptr_raw(image), i64(*image.stride()), _HEART_ELEM[image.dtype],
+                                ptr_raw(mask) if mask is not None else None, i64(*mask.stride()) if mask is not None else None,
+                                _HEART_LABEL[mask.dtype] if mask is not None else 0, i32(*n), i32(*m), ptr(bounds),
+                                int(integer if truncate is None else bool(truncate)), math.cos(rad), math.sin(rad), int(rotate),
+                                int(bool(zscore)), ptr(out), ptr(labels), ptr(raw_box), ptr(box), ptr(empty), ptr(stats), ptr(ws),
+                                ws.numel(), stream(image)), "sample_heart")
+    if strict and mask is not None and int(empty):
+        raise ValueError("resize_rotate_box: the label volume is empty (the reference's extract_bboxes raises here as well)")
+    return out, labels, raw_box, box, empty, stats
+
+
+def make_sample_heart(image_hwd, mask_hwd, angle, config, anchors, keys=None, strict=False):
+    """``make_sample`` in one pass: the loader's [H,W,D] image and label volumes (numpy or tensors, any size, their own dtype and
+    memory order) -> the dict ``train.train_epoch`` consumes, with load_image_gt's keys plus ``stats`` (mean, std of the z-score).
+    One difference from ``make_sample``, stated by the rule: an integer image is cast back to its dtype after the resize, as the
+    reference's resize_image and ``utils.mold_inputs`` do (``make_sample`` converts to float32 first and skips that cast)."""
+    dev = anchors.device
+    image = _volume(torch.as_tensor(image_hwd)).to(dev)
+    mask = _volume(torch.as_tensor(mask_hwd)).to(dev)
+    mx, mn = int(config.IMAGE_MAX_DIM), int(config.IMAGE_MIN_DIM)
+    img, labels, raw_box, box, empty, stats = resize_rotate_box(image, mask, (mx, mx, mn), angle, zscore=True, strict=strict)
+    nfg = int(config.NUM_CLASSES) - 1
+    boxf = box.to(torch.float32)[None]
+    rpn_match, rpn_bbox, counts = build_rpn_targets(anchors.to(dev), boxf, config, keys)
+    return dict(image=img[None, None], gt_class_ids=torch.arange(1, nfg + 1, device=dev), gt_boxes=boxf.repeat(nfg, 1),
+                gt_labels=labels, rpn_match=rpn_match, rpn_bbox_t=rpn_bbox, raw_box=raw_box, empty=empty, rpn_counts=counts,
+                stats=stats)
 
 
 # ------------------------------------------------------------------------------------------------------ the LiTS fork's sample
