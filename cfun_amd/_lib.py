@@ -183,6 +183,14 @@ HEART_SAMPLE_SIGNATURES = {
 }
 HEART_SAMPLE_EXPORTS = tuple(HEART_SAMPLE_SIGNATURES)
 
+# The warp entries (include/cfun_sample_warp.h): a table of their own, for the same reason; checked by tests/test_sample_warp_*.py.
+WARP_SAMPLE_SIGNATURES = {
+    "cfun_sample_warp_workspace_bytes": (_Z, [_P]),
+    "cfun_sample_warp_max_grid": (_I, []),
+    "cfun_sample_warp": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+}
+WARP_SAMPLE_EXPORTS = tuple(WARP_SAMPLE_SIGNATURES)
+
 # The output-tile query (include/cfun_tile.h): a host-side query in a table of its own, for the same reason.
 TILE_SIGNATURES = {
     "cfun_conv3d_fwd_tile": (C.c_int, [_PP, C.POINTER(C.c_int32)]),
@@ -264,7 +272,8 @@ def load():
             "`make -C cfun_amd/csrc -j8` or `python -c 'import __graft_entry__ as g; g.build()'`." % path)
     lib = C.CDLL(path)
     for name, (res, args) in list(_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(LITS_SAMPLE_SIGNATURES.items()) + \
-            list(NATIVE_SIGNATURES.items()) + list(HEART_SAMPLE_SIGNATURES.items()) + list(TILE_SIGNATURES.items()) + \
+            list(NATIVE_SIGNATURES.items()) + list(HEART_SAMPLE_SIGNATURES.items()) + list(WARP_SAMPLE_SIGNATURES.items()) + \
+            list(TILE_SIGNATURES.items()) + \
             list(EVAL_SIGNATURES.items()) + list(CC_SIGNATURES.items()) + list(SURFACE_SIGNATURES.items()) + \
             list(LESION_SIGNATURES.items()) + list(FILL_SIGNATURES.items()) + list(MORPH_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly

@@ -14,6 +14,10 @@
                         loader dtype), utils.resize_mask (order 0), the rotation, the box and utils.mold_image's z-score as one
                         gather pass, a finish launch and a flat pass; neither resized volume built   -- cfun_sample_heart
     make_sample_heart   resize_rotate_box plus the RPN targets: make_sample's dict
+    warp_and_box        elastic and affine augmentation of a network-size sample: a trilinear control-grid displacement, an
+                        in-plane affine map and flips as one gather pass, and the warped labels' box   -- cfun_sample_warp
+    Warp / draw_warp / affine_map   the holder of one warp, its host-side draw, and the six doubles of an in-plane map;
+                        ``augment=Warp`` on make_sample, make_sample_heart and make_sample_lits places the warp after the route
 
 Nothing on this path waits for the device: box, tiling and counts stay device tensors.  Only ``strict=True`` reads back (the
 empty flag and the label range) and raises where the reference would.
@@ -116,13 +120,16 @@ def build_rpn_targets(anchors, gt_boxes, config, keys=None):
     return rpn_match, rpn_bbox, counts
 
 
-def load_image_gt(image, mask, angle, config, anchors, keys=None, strict=False):
+def load_image_gt(image, mask, angle, config, anchors, keys=None, strict=False, augment=None):
     """model.load_image_gt on the device.  image / mask: the network-size [H,W,D] (or [H,W,D,1]) volumes; ``angle`` in degrees,
     ``None`` = the LiTS form (no rotation).  Returns the dict ``train.train_epoch`` consumes -- ``image`` [1,1,D,H,W] after
     utils.mold_image, ``gt_class_ids`` 1 .. NUM_CLASSES-1, ``gt_boxes`` the expanded box tiled NUM_CLASSES-1 times (float32
     voxels, as step.training_step_full takes them), ``gt_labels`` uint8 [D,H,W], ``rpn_match`` [1,A,1], ``rpn_bbox_t`` [1,R,6] --
-    plus ``raw_box``, ``empty`` and ``rpn_counts``."""
+    plus ``raw_box``, ``empty`` and ``rpn_counts``.  ``augment``: a ``Warp`` applied to the rotated sample before mold_image; box
+    and targets are then the warped labels'."""
     img, labels, raw_box, box, empty = rotate_and_box(image, mask, angle, strict=strict)
+    if augment is not None:
+        img, labels, raw_box, box, empty = warp_and_box(img, labels, augment)
     dev = img.device
     nfg = int(config.NUM_CLASSES) - 1
     boxf = box.to(torch.float32)[None]
@@ -132,16 +139,16 @@ def load_image_gt(image, mask, angle, config, anchors, keys=None, strict=False):
                 raw_box=raw_box, empty=empty, rpn_counts=counts)
 
 
-def make_sample(image_hwd, mask_hwd, angle, config, anchors, keys=None, strict=False):
+def make_sample(image_hwd, mask_hwd, angle, config, anchors, keys=None, strict=False, augment=None):
     """The loader's [H,W,D] image and label volumes (numpy or tensors, any size) -> a training sample: utils.resize_image /
-    resize_mask (mode 'self') to the network size, then load_image_gt."""
+    resize_mask (mode 'self') to the network size, then load_image_gt (``augment``: its ``Warp``)."""
     dev = anchors.device
     image = _volume(torch.as_tensor(image_hwd).to(dev))
     mask = _volume(torch.as_tensor(mask_hwd).to(dev))
     mx, mn = int(config.IMAGE_MAX_DIM), int(config.IMAGE_MIN_DIM)
     image = utils.resize_image(image[..., None].to(torch.float32), min_dim=mn, max_dim=mx, mode="self", device=dev)[0]
     mask = utils.resize_mask(mask, None, None, max_dim=mx, min_dim=mn, mode="self", device=dev)
-    return load_image_gt(image, mask, angle, config, anchors, keys=keys, strict=strict)
+    return load_image_gt(image, mask, angle, config, anchors, keys=keys, strict=strict, augment=augment)
 
 
 # ------------------------------------------------------------------------------------------- the heart sample in one pass
@@ -209,16 +216,24 @@ def resize_rotate_box(image, mask, out_shape, angle, zscore=True, strict=False, 
     return out, labels, raw_box, box, empty, stats
 
 
-def make_sample_heart(image_hwd, mask_hwd, angle, config, anchors, keys=None, strict=False):
+def make_sample_heart(image_hwd, mask_hwd, angle, config, anchors, keys=None, strict=False, augment=None):
     """``make_sample`` in one pass: the loader's [H,W,D] image and label volumes (numpy or tensors, any size, their own dtype and
     memory order) -> the dict ``train.train_epoch`` consumes, with load_image_gt's keys plus ``stats`` (mean, std of the z-score).
     One difference from ``make_sample``, stated by the rule: an integer image is cast back to its dtype after the resize, as the
-    reference's resize_image and ``utils.mold_inputs`` do (``make_sample`` converts to float32 first and skips that cast)."""
+    reference's resize_image and ``utils.mold_inputs`` do (``make_sample`` converts to float32 first and skips that cast).
+    ``augment``: a ``Warp``; the pass then runs without its z-score, the warp follows, and utils.mold_image normalises the warped
+    image (``stats`` are its mean and population std)."""
     dev = anchors.device
     image = _volume(torch.as_tensor(image_hwd)).to(dev)
     mask = _volume(torch.as_tensor(mask_hwd)).to(dev)
     mx, mn = int(config.IMAGE_MAX_DIM), int(config.IMAGE_MIN_DIM)
-    img, labels, raw_box, box, empty, stats = resize_rotate_box(image, mask, (mx, mx, mn), angle, zscore=True, strict=strict)
+    if augment is None:
+        img, labels, raw_box, box, empty, stats = resize_rotate_box(image, mask, (mx, mx, mn), angle, zscore=True, strict=strict)
+    else:
+        img, labels, _, _, _, _ = resize_rotate_box(image, mask, (mx, mx, mn), angle, zscore=False, strict=strict)
+        img, labels, raw_box, box, empty = warp_and_box(img, labels, augment)
+        stats = torch.stack([img.mean(), img.std(unbiased=False)]).to(torch.float64)
+        img = utils.mold_image(img)
     nfg = int(config.NUM_CLASSES) - 1
     boxf = box.to(torch.float32)[None]
     rpn_match, rpn_bbox, counts = build_rpn_targets(anchors.to(dev), boxf, config, keys)
@@ -292,19 +307,22 @@ def draw_angle(config, generator=None):
     return int(torch.randint(lo, hi, (1,), generator=generator))
 
 
-def make_sample_lits(image_hwd, mask_hwd, angle, config, anchors, keys=None, strict=False):
+def make_sample_lits(image_hwd, mask_hwd, angle, config, anchors, keys=None, strict=False, augment=None):
     """The LiTS fork's training sample (Dataset.__getitem__, LiTS_2017/model.py:1145-1248) from the loader's raw [H,W,D] arrays
     (numpy or tensors): the CT in HU, the label as int8 (what the fork stores), uint8 or int32.  ``angle``: degrees (the fork:
     ``draw_angle(config)`` when ``config.AUGMENTATION``), ``None`` = the fork's validation form (``augmentation=False``).
     Returns the dict ``train.train_epoch`` consumes, with load_image_gt's keys, plus ``window`` and ``image_meta`` as
     utils.mold_inputs_lits computes them.  ``image`` [1,1,D',H',W'] is the clamp-normalised volume WITHOUT utils.mold_image:
-    the fork never z-scores its input (its mold_inputs does not either)."""
+    the fork never z-scores its input (its mold_inputs does not either).  ``augment``: a ``Warp`` applied to the resized sample;
+    box and targets are then the warped labels'."""
     dev = anchors.device
     image = _volume(torch.as_tensor(image_hwd).to(dev))
     mask = _volume(torch.as_tensor(mask_hwd).to(dev))
     frame = [int(v) for v in config.PAD_IMAGE_SHAPE]
     h, w, d = [int(v) for v in config.IMAGE_SHAPE[:3]]
     img, labels, raw_box, box, empty = frame_rotate_resize(image, mask, frame, (h, w, d), angle=angle, normalise=True, strict=strict)
+    if augment is not None:
+        img, labels, raw_box, box, empty = warp_and_box(img, labels, augment)
     nfg = int(config.NUM_CLASSES) - 1
     boxf = box.to(torch.float32)[None]
     rpn_match, rpn_bbox, counts = build_rpn_targets(anchors, boxf, config, keys)
@@ -316,3 +334,128 @@ def make_sample_lits(image_hwd, mask_hwd, angle, config, anchors, keys=None, str
     return dict(image=img[None, None], gt_class_ids=torch.arange(1, nfg + 1, device=dev), gt_boxes=boxf.repeat(nfg, 1),
                 gt_labels=labels, rpn_match=rpn_match, rpn_bbox_t=rpn_bbox, raw_box=raw_box, empty=empty, rpn_counts=counts,
                 window=window, image_meta=meta)
+
+
+# ---------------------------------------------------------------------------------- elastic and affine augmentation: one warp
+class Warp:
+    """One warp of include/cfun_sample_warp.h, a plain holder.  ``grid``: float32 [3,gz,gy,gx] displacements in voxels (z, y, x
+    components; a tensor or a numpy array) or ``None``; ``map``: six doubles (``affine_map``) or ``None``; ``flips``: one bool
+    per axis (z, y, x); ``image_order`` 0 or 1 (the labels are always nearest).  ``factor``: what ``draw_warp`` scaled the drawn
+    grid by to keep the map one-to-one (1.0: nothing)."""
+
+    def __init__(self, grid=None, map=None, flips=(False, False, False), image_order=1, factor=1.0):
+        self.grid, self.map, self.flips, self.image_order, self.factor = grid, map, tuple(bool(f) for f in flips), int(image_order), factor
+
+    def __repr__(self):
+        g = None if self.grid is None else tuple(self.grid.shape)
+        return "Warp(grid=%s, map=%s, flips=%s, image_order=%d, factor=%r)" % (g, self.map, self.flips, self.image_order, self.factor)
+
+
+def affine_map(angle, h, w, scale=(1, 1), translate=(0, 0)):
+    """The six doubles of the INVERSE in-plane map (cfun_sample_lits.h's convention: col = m0 x + m1 y + m2, row = m3 x + m4 y +
+    m5) of: zoom by ``scale`` = (sy, sx) about the centre of an [h, w] slice, rotate by ``angle`` degrees about it, move by
+    ``translate`` = (ty, tx) voxels.  With the defaults it equals ``rotation_map(angle, h, w)`` exactly."""
+    t = math.radians(float(angle))
+    c, s = math.cos(t), math.sin(t)
+    cx, cy = w / 2 - 0.5, h / 2 - 0.5
+    sy, sx = float(scale[0]), float(scale[1])
+    ty, tx = float(translate[0]), float(translate[1])
+    m0, m1, m3, m4 = c / sx, -s / sy, s / sx, c / sy
+    return (m0, m1, cx - m0 * (cx + tx) - m1 * (cy + ty), m3, m4, cy - m3 * (cx + tx) - m4 * (cy + ty))
+
+
+def _fold_ratio(grid, shape_dhw):
+    """max over the components c of |difference of neighbouring control values along axis c| / (half a cell along c, in voxels)."""
+    worst = 0.0
+    for c in range(3):
+        n, g = int(shape_dhw[c]), int(grid.shape[1 + c])
+        if n == 1:
+            continue               # (only control plane 0 acts along an axis of extent 1: nothing can fold)
+        half = 0.5 * (n - 1) / (g - 1)
+        worst = max(worst, float(grid[c].to(torch.float64).diff(dim=c).abs().max()) / half)
+    return worst
+
+
+def draw_warp(shape_dhw, generator=None, grid=(5, 5, 5), sigma=(2.0, 4.0, 4.0), angle=None, scale_range=None, flip_p=(0, 0, 0),
+              image_order=1):
+    """Draw one ``Warp`` for a [D,H,W] sample on the host, from the CPU torch.Generator ``generator`` (as ``draw_angle`` draws):
+    control values ~ N(0, sigma_c) voxels per component (``sigma``: a number or one per z, y, x), an angle uniform in
+    ``angle`` = (lo, hi) degrees (a number: that angle; ``None``: no rotation), a zoom per in-plane axis uniform in
+    ``scale_range`` = (lo, hi), a flip per axis with probability ``flip_p``.  The draws are made in this order, all of them
+    always, so one generator state gives one Warp whatever the switches.
+    The map stays one-to-one along each component's own axis: where two neighbouring control values of component c differ by more
+    than half a control cell along axis c, (n_c - 1) / (g_c - 1) / 2 voxels, the whole grid is scaled down until the float32
+    values meet the bound; ``Warp.factor`` is that factor."""
+    shape_dhw = tuple(int(v) for v in shape_dhw)
+    g = tuple(int(v) for v in grid)
+    if len(shape_dhw) != 3 or min(shape_dhw) <= 0 or len(g) != 3 or min(g) < 2:
+        raise ValueError("draw_warp: a positive [D,H,W] shape and a control grid of at least 2 points per axis expected")
+    sig = torch.tensor([float(sigma)] * 3 if np.isscalar(sigma) else [float(v) for v in sigma], dtype=torch.float64)
+    field = torch.randn((3,) + g, generator=generator, dtype=torch.float64) * sig[:, None, None, None]
+    u = [float(v) for v in torch.rand(6, generator=generator, dtype=torch.float64)]      # (host tensors: nothing reads a device back)
+    factor, values = 1.0, field.to(torch.float32)
+    for _ in range(8):
+        r = _fold_ratio(values, shape_dhw)
+        if r <= 1.0:
+            break
+        factor = factor / r * (1.0 - 2.0 ** -20)
+        values = (field * factor).to(torch.float32)
+    else:
+        raise RuntimeError("draw_warp: the control grid could not be scaled under the half-cell bound")
+    amap = None
+    if angle is not None or scale_range is not None:
+        if angle is None:
+            a = 0.0
+        elif np.isscalar(angle):
+            a = float(angle)
+        else:
+            a = float(angle[0]) + u[0] * (float(angle[1]) - float(angle[0]))
+        sc = (1.0, 1.0)
+        if scale_range is not None:
+            lo, hi = float(scale_range[0]), float(scale_range[1])
+            sc = (lo + u[1] * (hi - lo), lo + u[2] * (hi - lo))
+        amap = affine_map(a, shape_dhw[1], shape_dhw[2], scale=sc)
+    flips = tuple(u[3 + k] < float(flip_p[k]) for k in range(3))
+    return Warp(values, amap, flips, image_order, factor)
+
+
+def warp_and_box(image_dhw, labels_dhw, warp):
+    """image float32 [D,H,W], labels uint8 [D,H,W] on the device (what every sample route yields before utils.mold_image), ``warp``
+    a ``Warp``.  The rule is include/cfun_sample_warp.h's.  Returns (image [D,H,W] float32, labels [D,H,W] uint8, raw_box
+    int32[6], box int32[6], empty int32[1]) on the device; nothing waits for it."""
+    lib = _lib.load()
+    if image_dhw.dim() != 3 or tuple(image_dhw.shape) != tuple(labels_dhw.shape):
+        raise ValueError("warp_and_box: [D,H,W] image and labels of one shape expected, got %s and %s"
+                         % (tuple(image_dhw.shape), tuple(labels_dhw.shape)))
+    if image_dhw.device != labels_dhw.device:
+        raise ValueError("warp_and_box: image and labels sit on different devices")
+    if labels_dhw.dtype != torch.uint8:
+        raise ValueError("warp_and_box: uint8 labels expected, got %s" % (labels_dhw.dtype,))
+    dev = image_dhw.device
+    image = image_dhw.to(torch.float32).contiguous()
+    labels = labels_dhw.contiguous()
+    n = [int(v) for v in image.shape]
+    if min(n) <= 0 or n[0] * n[1] * n[2] >= 1 << 31:
+        raise ValueError("warp_and_box: unsupported extent %s" % (n,))
+    i32 = C.c_int32 * 3
+    grid = gdims = None
+    if warp.grid is not None:
+        grid = torch.as_tensor(warp.grid).to(device=dev, dtype=torch.float32).contiguous()
+        top = int(lib.cfun_sample_warp_max_grid())
+        if grid.dim() != 4 or grid.shape[0] != 3 or min(grid.shape[1:]) < 2 or max(grid.shape[1:]) > top:
+            raise ValueError("warp_and_box: a [3,gz,gy,gx] control grid with 2 .. %d points per axis expected, got %s"
+                             % (top, tuple(grid.shape)))
+        gdims = i32(*[int(v) for v in grid.shape[1:]])
+    if warp.image_order not in (0, 1):
+        raise ValueError("warp_and_box: image_order 0 or 1 expected, got %r" % (warp.image_order,))
+    amap = (C.c_double * 6)(*[float(v) for v in warp.map]) if warp.map is not None else None
+    flips = sum(1 << k for k in range(3) if warp.flips[k])
+    ws = workspace(lib.cfun_sample_warp_workspace_bytes(i32(*n)), image)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    out_labels = torch.empty(n, dtype=torch.uint8, device=dev)
+    small = torch.empty(16, dtype=torch.int32, device=dev)
+    raw_box, box, empty = small[0:6], small[6:12], small[12:13]
+    check(lib.cfun_sample_warp(ptr(image), ptr(labels), i32(*n), ptr(grid), gdims, amap, flips, warp.image_order, ptr(out),
+                               ptr(out_labels), ptr(raw_box), ptr(box), ptr(empty), ptr(ws), ws.numel(), stream(image)),
+          "sample_warp")
+    return out, out_labels, raw_box, box, empty
